@@ -9,22 +9,29 @@ chain over the N GPUs instead (strong scaling, e.g. the north_star's 1M-round ch
 rank verifies its rounds once (fresh CSPRNG seed); with N > 1 each batch runs under the node-wide check: the ranks'
 level-0 RLC sums are all-gathered over RCCL and ONE pairing check covers the node (drand_amd/dist.py), queued
 without a host wait; the verdict bitmaps are all-gathered at the end of the timed steps. With N > 1 under weak scaling
-the line also carries "strong_scaling": the north_star's shape, ONE 1,048,576-round chain split over the N ranks
+and --full the line also carries "strong_scaling": the north_star's shape, ONE 1,048,576-round chain split over the N ranks
 (--strong-total-rounds), timed the same way after the weak leg.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--total-rounds n | --rounds-per-gpu n] [--scheme name]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches the N ranks itself (a child
 `python -m torch.distributed.run`, started before this process touches the GPU) and exits with its status; rank 0's
 JSON line is the output. Under a launcher, WORLD_SIZE must equal --gpus.
 
-Rank 0 prints ONE JSON line: value = rounds verified by all ranks / max-over-ranks wall time of the K steps.
+Rank 0 prints ONE JSON line: value = rounds verified by all ranks / max-over-ranks wall time of the K steps, and
+ms_per_step = that wall time / K. A plain run does no more than that: set-up, warm-up, the K timed steps, the check that
+every synthetic round verified, the line. --dump-outputs DIR also writes what the last timed step returned (see
+dump_outputs; the inputs are the same from run to run, so two builds can be compared output for output). The legs
+below, each a run of its own after the timed steps, need --full; without it their fields are null:
+"strong_scaling" (above).
 "roofline": the dominant kernel's integer-multiply rate (its algorithmic mul32 per launch, bench/workmodel.json, over
 its HIP-event duration on its own stream) against the measured v_mad_u64_u32 peak (bench/microbench_mul.hip).
 "cpu_baseline": the CPU oracle (a C restatement of the reference's per-round VerifyBeacon, oracle/bls_oracle.c) on a
 bounded sample, on the host cores this process may use. "single_call": one dh_verify_batch_device call at a time
-(the drop-in callers' shape), split by the library over its internal streams.
+(the drop-in callers' shape), split by the library over its internal streams. "single_beacon_ms": one-beacon calls
+(bench/single_beacon.py).
 """
 import argparse
 import collections
@@ -60,6 +67,13 @@ def parse():
                     help="N > 1, weak scaling: also time ONE chain of this many rounds split over the N ranks and report "
                          "it as strong_scaling (0: skip)")
     ap.add_argument("--scheme", default="bls-unchained-g1-rfc9380")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the secondary legs: strong_scaling (N > 1), roofline, "
+                         "single_call, single_beacon_ms, cpu_baseline (each still has its own switch below); without "
+                         "it the run sets up, warms up, times the steps and prints the line with those fields null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (per-round verdicts and "
+                         "randomness, float32) as DIR/<name>.npy")
     ap.add_argument("--cpu-sample-seconds", type=float, default=8.0,
                     help="wall time of the bounded CPU-baseline sample (after the GPU legs; kept short so the GPU work is "
                          "not a small share of the run)")
@@ -93,7 +107,13 @@ def parse():
     ap.add_argument("--exchange", choices=["auto", "always"], default="auto",
                     help="always: run the node step's collectives at N = 1 too, over a one-rank process group (the "
                          "RCCL branch rehearsed on one GPU; RCCL takes one rank per GPU)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run: the headline figure only
+        args.strong_total_rounds = args.roofline_steps = args.single_call_steps = args.single_beacon_reps = 0
+        args.no_cpu_baseline = True
+    return args
 
 
 def load_workmodel():
@@ -144,6 +164,22 @@ def cpu_baseline(scheme, pk, rounds, sigs, seconds):
             "cpu_model": model, "affinity_cpus": affinity, "cgroup_cpu_quota": quota,
             "sample": "%d quicknet rounds (the first of the synthetic chain): per-round decode + subgroup (r*P) + "
                       "hash + 2-pairing VerifyBeacon (CPU restatement, not kyber), %d threads, %.1f s" % (n, threads, dt)}
+
+
+def dump_outputs(path, d_verdict, d_rand, rank, world):
+    """What the last timed step handed its caller, as float32 .npy files under `path`: verdict [rows] (0/1) and
+    randomness [rows, 32] (byte values) of this rank's rounds, with rows [rows] (float64) naming the rounds' indices
+    in the rank's shard. Every round up to 262144 / world of them; above that a fixed sorted sample of that many
+    (generator seed 0), which keeps all ranks' files together under 64 MB. Ranks other than 0 of an N > 1 run add
+    _rank<r> to the names."""
+    n = d_verdict.shape[0]
+    cap = (1 << 18) // world
+    rows = np.arange(n) if n <= cap else np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+    tag = "" if rank == 0 else "_rank%d" % rank
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rows%s.npy" % tag), rows.astype(np.float64))
+    np.save(os.path.join(path, "verdict%s.npy" % tag), d_verdict.cpu().numpy()[rows].astype(np.float32))
+    np.save(os.path.join(path, "randomness%s.npy" % tag), d_rand.cpu().numpy()[rows].astype(np.float32))
 
 
 def launch_ranks(args):
@@ -235,6 +271,7 @@ def main():
             self.d_part = [torch.zeros(pbytes, dtype=torch.uint8, device=dev) for _ in range(2 * S)]
             self.packed = [None] * (2 * S)
             self.used = set()
+            self.last = None  # the slot of the newest batch of the last run_steps
 
         def take(self, slot):
             ev = self.packed[slot]
@@ -298,7 +335,7 @@ def main():
         for k in range(k_steps):
             if len(pending) == streams:
                 retire()
-            slot = wk.take(k % (2 * streams))
+            wk.last = slot = wk.take(k % (2 * streams))
             # the record, the collective and the check of a batch run on that batch's own library stream
             # (dist.begin_node_batch): no stream shared by the batches carries a wait for another batch's record (r04a
             # ordered them all through torch's current stream and chained every batch's per-round kernels behind the
@@ -331,6 +368,8 @@ def main():
                 torch.cuda.set_device(dev_index)
                 for j, k in enumerate(range(t, k_steps, streams)):
                     slot = wk.take(2 * t + (j & 1))
+                    if k == k_steps - 1:
+                        wk.last = slot
                     verify(wk, slot)
                     bits[k] = wk.pack(slot)
             except Exception as e:  # surfaced below
@@ -373,6 +412,8 @@ def main():
     state["node_host_s"] = collections.Counter()  # the timed region's host time per pipeline phase
     elapsed = timed(work, args.steps)
     prof = profile_read()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, work.d_verdict[work.last], work.d_rand[work.last], rank, world)
     # sanity (outside the timed region): every synthetic round verifies, randomness = SHA-256(sig)
     ok = work.all_valid()
     r0 = work.d_rand[min(work.used)].cpu().numpy()[0].tobytes()

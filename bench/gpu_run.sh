@@ -16,6 +16,8 @@
 #   rocprofpy:<script args> rocprofv3 --kernel-trace --stats of python3 <script args> -> gpurun_out/prof_<tag>_<i>/
 #   env:<NAME>=<value>     export a variable for the steps after it (env:NAME= clears it)
 #   sh:<script args>       bash <script args> (bench/pmc.sh, bench/bisect_sweep.sh: they time-limit their own steps)
+# bench.py alone times its headline steps; its roofline, single_call, single_beacon_ms and cpu_baseline legs (and the
+# roofline dispatches that bench/rocpd_stats.py --last 2 averages) need bench:--full / rocprof:--full.
 set -euo pipefail
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out

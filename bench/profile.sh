@@ -1,7 +1,7 @@
 #!/bin/bash
 # Profiling recipe for the headline bench (run on the GPU box from the repo root):
 #   bash bench/profile.sh <tag>
-# 1. rocprofv3 --kernel-trace --stats over the default bench command (1M quicknet rounds, 8 batches in flight,
+# 1. rocprofv3 --kernel-trace --stats over the bench command with --full (1M quicknet rounds, 8 batches in flight,
 #    then bench.py's 2 single-stream roofline batches) -> bench/rocpd_stats.py --last 2 gives the per-kernel
 #    average over exactly the launches bench.py's HIP-event roofline measures;
 # 2. --pmc passes over one single-stream 262144-round batch, one counter group per run as MI355X_MICROARCH.md
@@ -16,7 +16,7 @@ O=$R/gpurun_out
 mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$O/prof_$TAG" -o run --output-format csv -- \
-  python3 "$R/bench.py" --steps 8 --warmup 8 --single-call-steps 0 --single-beacon-reps 0 --no-cpu-baseline > "$O/prof_$TAG.log" 2>&1
+  python3 "$R/bench.py" --full --steps 8 --warmup 8 --single-call-steps 0 --single-beacon-reps 0 --no-cpu-baseline > "$O/prof_$TAG.log" 2>&1
 SMALL="--total-rounds 262144 --steps 1 --warmup 0 --streams 1 --roofline-steps 0 --single-call-steps 0 --single-beacon-reps 0 --no-cpu-baseline"
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d "$O/pmc_fetch_$TAG" -o pmc --output-format csv -- python3 "$R/bench.py" $SMALL \
   > "$O/pmc_fetch_$TAG.log" 2>&1

@@ -430,7 +430,8 @@ def test_bench_launches_ranks():
     """`python bench.py --gpus 2` with no launcher spawns the two ranks itself (torch.distributed.run in a child
     process, before any HIP call) and prints rank 0's line: n_gpus 2, the node-wide check as the parallelism, every
     verdict valid. gloo rehearsal: both ranks on GPU 0, strong scaling of a 262,144-round chain; then weak scaling,
-    whose line also carries the strong_scaling field (one chain split over the ranks, the north_star's shape)."""
+    whose line under --full also carries the strong_scaling field (one chain split over the ranks, the north_star's
+    shape)."""
     import subprocess
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
@@ -444,7 +445,7 @@ def test_bench_launches_ranks():
     assert res["n_gpus"] == 2 and res["verdicts_ok"] is True and res["scaling"] == "strong"
     assert "node-wide RLC check" in res["config"]["parallelism"] and res["config"]["rounds_per_gpu"] == 131072
     assert res["strong_scaling"] is None  # the value itself is the strong figure
-    out = subprocess.run(base + ["--rounds-per-gpu", "65536", "--strong-total-rounds", "131072"], env=env,
+    out = subprocess.run(base + ["--full", "--rounds-per-gpu", "65536", "--strong-total-rounds", "131072"], env=env,
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     res = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][0])
