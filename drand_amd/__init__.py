@@ -6,6 +6,7 @@ over that ABI; see drand_amd.scheme.
 """
 from .scheme import (  # noqa: F401
     Scheme,
+    AuthScheme,
     SchemeError,
     DeviceError,
     DeviceBusy,

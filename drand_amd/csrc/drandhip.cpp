@@ -122,6 +122,10 @@ struct worker {
   dbuf r_commits, r_cstatus, r_caff, r_shares, r_raw, r_psigs, r_pidx, r_pstatus, r_paff, r_msgs, r_q, r_scal,
       r_round_of, r_e_pidx, r_e_sidx, r_e_grp, r_P, r_Q, r_f, r_skip, r_ok, r_sel, r_lam, r_lamset, r_rok, r_sig,
       r_sigbytes, r_status2, r_aff2, r_entries2, r_off, r_key, r_den, r_zs, r_tbl, r_rstat, r_ltmp, r_own, r_need;
+  // batch Verify under many keys (auth_core): the key table (raw, decode status, affine, per-key Jacobian), the items'
+  // key indices and message offsets, the per-key signature sums (Jacobian, compressed, affine, status), the per-key
+  // check results and the leaf list
+  dbuf a_keys, a_kstatus, a_kaff, a_shares, a_kidx, a_moff, a_Ak, a_Akbytes, a_Akaff, a_Akstat, a_kpass, a_list;
   std::vector<uint8_t> h_verdict;
   // Recover: the (scheme, t, n_nodes, commits) whose decoded commits and public shares r_caff / r_shares hold
   std::vector<uint8_t> r_pub_key;
@@ -151,7 +155,9 @@ struct worker {
                    &scan_tmp, &list, &buckets, &segs, &outA, &outB, &out2, &pass, &part, &meta, &vm_pairs, &vm_live, &vm_done, &r_commits, &r_cstatus, &r_caff, &r_shares,
                    &r_raw, &r_psigs, &r_pidx, &r_pstatus, &r_paff, &r_msgs, &r_q, &r_scal, &r_round_of, &r_e_pidx,
                    &r_e_sidx, &r_e_grp, &r_P, &r_Q, &r_f, &r_skip, &r_ok, &r_sel, &r_lam, &r_lamset, &r_rok, &r_sig,
-                   &r_sigbytes, &r_status2, &r_aff2, &r_entries2, &r_off, &r_key, &r_den, &r_zs, &r_tbl, &r_rstat, &r_ltmp, &r_own, &r_need, &node_sum, &node_res};
+                   &r_sigbytes, &r_status2, &r_aff2, &r_entries2, &r_off, &r_key, &r_den, &r_zs, &r_tbl, &r_rstat, &r_ltmp, &r_own, &r_need, &node_sum, &node_res,
+                   &a_keys, &a_kstatus, &a_kaff, &a_shares, &a_kidx, &a_moff, &a_Ak, &a_Akbytes, &a_Akaff, &a_Akstat, &a_kpass,
+                   &a_list};
     for (dbuf* b : all) b->release();
     d_stage.release();
     sub_bad.release();
@@ -400,6 +406,59 @@ struct sha256_host {
     }
   }
 };
+
+// ---- host BLAKE2b-256 (RFC 7693, unkeyed): Identity.Hash of key/keys.go:53-57 for dh_identity_hash_batch
+void blake2b_256(const uint8_t* in, size_t len, uint8_t out[32]) {
+  static const uint64_t iv[8] = {0x6a09e667f3bcc908ULL, 0xbb67ae8584caa73bULL, 0x3c6ef372fe94f82bULL, 0xa54ff53a5f1d36f1ULL,
+                                 0x510e527fade682d1ULL, 0x9b05688c2b3e6c1fULL, 0x1f83d9abfb41bd6bULL, 0x5be0cd19137e2179ULL};
+  static const uint8_t sigma[12][16] = {
+      {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
+      {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
+      {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
+      {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
+      {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0},
+      {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3}};
+  auto ror = [](uint64_t x, int k) { return (x >> k) | (x << (64 - k)); };
+  uint64_t h[8];
+  memcpy(h, iv, sizeof h);
+  h[0] ^= 0x01010000ULL ^ 32;  // digest length 32, no key, fanout = depth = 1
+  size_t done = 0;
+  for (bool last = false; !last;) {
+    uint8_t blk[128] = {0};
+    const size_t take = std::min<size_t>(128, len - done);
+    memcpy(blk, in + done, take);
+    done += take;
+    last = done == len;  // the last block may be full; an empty input is one zero block
+    uint64_t m[16], v[16];
+    for (int i = 0; i < 16; i++) {
+      m[i] = 0;
+      for (int b = 7; b >= 0; b--) m[i] = (m[i] << 8) | blk[8 * i + b];
+    }
+    memcpy(v, h, sizeof h);
+    memcpy(v + 8, iv, sizeof iv);
+    v[12] ^= (uint64_t)done;
+    if (last) v[14] = ~v[14];
+    for (int r = 0; r < 12; r++) {
+      const uint8_t* s = sigma[r];
+      auto G = [&](int a, int b, int c, int d, uint64_t x, uint64_t y) {
+        v[a] = v[a] + v[b] + x; v[d] = ror(v[d] ^ v[a], 32);
+        v[c] = v[c] + v[d];     v[b] = ror(v[b] ^ v[c], 24);
+        v[a] = v[a] + v[b] + y; v[d] = ror(v[d] ^ v[a], 16);
+        v[c] = v[c] + v[d];     v[b] = ror(v[b] ^ v[c], 63);
+      };
+      G(0, 4, 8, 12, m[s[0]], m[s[1]]);
+      G(1, 5, 9, 13, m[s[2]], m[s[3]]);
+      G(2, 6, 10, 14, m[s[4]], m[s[5]]);
+      G(3, 7, 11, 15, m[s[6]], m[s[7]]);
+      G(0, 5, 10, 15, m[s[8]], m[s[9]]);
+      G(1, 6, 11, 12, m[s[10]], m[s[11]]);
+      G(2, 7, 8, 13, m[s[12]], m[s[13]]);
+      G(3, 4, 9, 14, m[s[14]], m[s[15]]);
+    }
+    for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
+  }
+  for (int i = 0; i < 32; i++) out[i] = (uint8_t)(h[i / 8] >> (8 * (i % 8)));
+}
 
 uint64_t splitmix64(uint64_t& x) {
   uint64_t z = (x += 0x9e3779b97f4a7c15ULL);
@@ -1472,6 +1531,232 @@ int recover_core(worker* w, int scheme, const uint8_t* commits, int t, int n_nod
   return DH_OK;
 }
 
+// ---- sign.Scheme.Verify in batch under keys the caller passes (dh_bls_verify_batch: the schemes' AuthScheme,
+// crypto/schemes.go:102,143,183, and the identity self-signatures of key/keys.go:61-64). recover_core's batched
+// VerifyPartial with a key table in place of the public polynomial's shares, one hash point per item and messages of
+// any length. Three levels, verdicts exact at each:
+//   1  A = sum r_i sigma_i, B_k = sum over the items of key k of r_i Q_i, one (n_keys + 1)-pair product check
+//   2  (level 1 failed, more than one key in use) A_k per key, one 2-pair check per key: the failing keys
+//   3  leaf checks of the items under failing keys; the items of passing keys are valid when they decoded
+// Leaf checks only (no scalars, no MSM) for n <= small_batch_max() or fewer than auth_rlc_min_per_key() items per key
+// in use. DRANDHIP_AUTH_PATH=leaf|rlc forces either path; it is read at every call.
+// T = 2 items per key, measured at n = 4096 (profiles/r07/auth_measure.json): leaf checks 50.7 ms (quicknet) / 54.2 ms
+// (pedersen-bls-unchained) whatever the keys; rlc 12.4 / 20.9 ms under one key, 29.8 / 37.7 ms at 2 items per key,
+// 48.6 / 55.5 ms at one item per key (the product's n_keys + 1 Miller loops), where it no longer wins for both.
+static size_t auth_rlc_min_per_key() { return 2; }
+
+enum { AUTH_AUTO = 0, AUTH_LEAF, AUTH_RLC };
+static int auth_path_env() {
+  const char* e = getenv("DRANDHIP_AUTH_PATH");
+  if (e && !strcmp(e, "leaf")) return AUTH_LEAF;
+  if (e && !strcmp(e, "rlc")) return AUTH_RLC;
+  return AUTH_AUTO;
+}
+
+// kidx: n key indices < n_keys (host); keys_used: distinct values among them; off: n + 1 message offsets from 0 (host)
+int auth_core(worker* w, int scheme, const uint8_t* keys, size_t n_keys, const uint32_t* kidx, size_t keys_used,
+              const uint8_t* msgs, const uint32_t* off, const uint8_t* sigs, size_t sig_stride, size_t n, uint8_t* verdict_out,
+              uint8_t* key_ok_out, uint64_t seed, uint64_t stats[4], hipStream_t st) {
+  const bool g2 = sig_on_g2(scheme);
+  const int sl = g2 ? 96 : 48, kl = g2 ? 48 : 96;
+  const size_t jw = g2 ? JAC_WORDS_G2 : JAC_WORDS_G1, aw = jw * 2 / 3;
+  const size_t kjw = g2 ? JAC_WORDS_G1 : JAC_WORDS_G2, kaw = kjw * 2 / 3;
+  const size_t total = off[n], nmax = std::max(n, n_keys);
+  timed_launches T(st);
+  // 1. the key table: decode + subgroup test, one lane per key (the signature kernels of the key group), then the
+  // per-key layout of the pair and leaf kernels
+  HIP_TRY(w->a_keys.ensure(n_keys * kl + 4));
+  HIP_TRY(w->a_kstatus.ensure(n_keys + 4));
+  HIP_TRY(w->a_kaff.ensure(n_keys * kaw * 4 + 16));
+  HIP_TRY(w->a_shares.ensure(n_keys * kjw * 4));
+  HIP_TRY(hipMemcpyAsync(w->a_keys.p, keys, n_keys * kl, hipMemcpyHostToDevice, st));
+  HIP_TRY(T.run(g2 ? "k_prep_sig<fp>(keys)" : "k_prep_sig<fp2>(keys)", [&] {
+    return dh::launch_prep(g2 ? 0 : 1, w->a_keys.as<uint8_t>(), kl, n_keys, w->a_kstatus.as<uint8_t>(), w->a_kaff.as<uint32_t>(),
+                           nullptr, st);
+  }));
+  HIP_TRY(dh::launch_key_shares(g2 ? 0 : 1, w->a_kaff.as<uint32_t>(), w->a_kstatus.as<uint8_t>(), n_keys,
+                                w->a_shares.as<uint32_t>(), st));
+  // 2. signatures: decode + subgroup test; an item under a bad key is rejected with them
+  HIP_TRY(w->r_raw.ensure(n * sig_stride + 4));
+  HIP_TRY(w->r_pstatus.ensure(n + 4));
+  HIP_TRY(w->r_paff.ensure(n * aw * 4 + 16));
+  HIP_TRY(w->a_kidx.ensure(n * 4 + 4));
+  HIP_TRY(hipMemcpyAsync(w->r_raw.p, sigs, n * sig_stride, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w->a_kidx.p, kidx, n * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(T.run(g2 ? "k_prep_sig<fp2>(auth)" : "k_prep_sig<fp>(auth)", [&] {
+    return dh::launch_prep(g2, w->r_raw.as<uint8_t>(), sig_stride, n, w->r_pstatus.as<uint8_t>(), w->r_paff.as<uint32_t>(),
+                           nullptr, st);
+  }));
+  HIP_TRY(dh::launch_mark_bad_key(w->a_kidx.as<uint32_t>(), n, w->a_kstatus.as<uint8_t>(), w->r_pstatus.as<uint8_t>(), st));
+  // 3. hash points: the fixed-shape kernels when every message is 32 bytes (identity hashes, beacon digests), else the
+  // variable-length form
+  bool all32 = true;
+  for (size_t i = 0; i < n && all32; i++) all32 = off[i + 1] - off[i] == 32;
+  HIP_TRY(w->r_msgs.ensure(total + 4));
+  HIP_TRY(w->r_q.ensure(n * jw * 4));
+  HIP_TRY(w->h2c_tmp.ensure(dh::hash_tmp_bytes(g2, n)));
+  if (total) HIP_TRY(hipMemcpyAsync(w->r_msgs.p, msgs, total, hipMemcpyHostToDevice, st));
+  if (all32) {
+    HIP_TRY(T.run(g2 ? "k_prep_msg32<fp2>" : "k_prep_msg32<fp>", [&] {
+      return dh::launch_hash(g2, nullptr, nullptr, 0, nullptr, w->r_msgs.as<uint8_t>(), n, 0, dst_id(scheme), nullptr,
+                             w->r_q.as<uint32_t>(), w->h2c_tmp.as<uint32_t>(), st);
+    }));
+  } else {
+    HIP_TRY(w->a_moff.ensure((n + 1) * 4));
+    HIP_TRY(hipMemcpyAsync(w->a_moff.p, off, (n + 1) * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(T.run(g2 ? "k_prep_msgv<fp2>" : "k_prep_msgv<fp>", [&] {
+      return dh::launch_hash_var(g2, w->r_msgs.as<uint8_t>(), w->a_moff.as<uint32_t>(), n, dst_id(scheme), w->r_q.as<uint32_t>(),
+                                 w->h2c_tmp.as<uint32_t>(), st);
+    }));
+  }
+  // item i is entry i, its own hash point i, under key kidx[i]
+  HIP_TRY(w->entries.ensure(nmax * 4 + 4));
+  HIP_TRY(dh::launch_iota(w->entries.as<uint32_t>(), nmax, st));
+  HIP_TRY(w->r_ok.ensure(n + 4));
+  const uint32_t* iota = w->entries.as<uint32_t>();
+  auto leaves = [&](const uint32_t* list, size_t m) {
+    return T.run("k_partial_leaf(auth)", [&] {
+      return dh::launch_partial_leaf(g2, list, m, w->r_paff.as<uint32_t>(), w->r_pstatus.as<uint8_t>(), w->a_kidx.as<uint32_t>(),
+                                     iota, w->r_q.as<uint32_t>(), w->a_shares.as<uint32_t>(), (int)n_keys, w->r_ok.as<uint8_t>(), st);
+    });
+  };
+  uint64_t levels = 0, keys_failed = 0, leaf_items = 0;
+  const int forced = auth_path_env();
+  const bool leaf_only =
+      forced == AUTH_LEAF || (forced == AUTH_AUTO && (n <= small_batch_max() || n < auth_rlc_min_per_key() * keys_used));
+  if (leaf_only) {
+    HIP_TRY(leaves(iota, n));
+    leaf_items = n;
+  } else {
+    // level 1: RLC scalars (0 for rejected items), the two MSMs, the product check
+    const int parts = g2 ? 4 : 2;
+    const size_t pw28 = g2 ? 64 : 32, wsw = g2 ? 96 : 48;
+    uint32_t seedw[8];
+    int rc = make_seed(seed, seedw);
+    if (rc) return rc;
+    HIP_TRY(w->key_ok.ensure(64));
+    uint32_t* d_seed = (uint32_t*)((uint8_t*)w->key_ok.p + 32);
+    HIP_TRY(hipMemcpyAsync(d_seed, seedw, 32, hipMemcpyHostToDevice, st));
+    HIP_TRY(w->r_scal.ensure(n * 16 + 16));
+    HIP_TRY(dh::launch_scalars(d_seed, n, w->r_pstatus.as<uint8_t>(), w->r_scal.as<uint4>(), parts, st));
+    HIP_TRY(w->s28.ensure(parts * n * pw28 * 4));
+    HIP_TRY(w->q28.ensure(parts * n * pw28 * 4));
+    HIP_TRY(w->r_rstat.ensure(n));
+    HIP_TRY(hipMemsetAsync(w->r_rstat.p, 1 /* DEC_OK */, n, st));
+    HIP_TRY(dh::launch_msm_prep28(g2, n, w->r_pstatus.as<uint8_t>(), w->r_paff.as<uint32_t>(), nullptr, w->s28.as<uint32_t>(),
+                                  nullptr, st, 1));
+    HIP_TRY(dh::launch_msm_prep28(g2, n, w->r_rstat.as<uint8_t>(), nullptr, w->r_q.as<uint32_t>(), nullptr, w->q28.as<uint32_t>(),
+                                  st, 2));
+    dh::msm_geom gA = geom_for(n, parts);
+    gA.half_stride = (uint32_t)n;
+    dh::msm_geom gB = geom_for(std::max<size_t>(1, n / keys_used), parts);  // window geometry from the items per key in use
+    while (gB.c > 3 && n_keys * gB.nwin * gB.nbuck > ((size_t)1 << 24))
+      gB = geom_for(std::max<size_t>(1, ((size_t)1 << (gB.c + 1)) / parts), parts);
+    gB.half_stride = (uint32_t)n;
+    // one workspace for both (sized for each before anything is queued on it), used one MSM after the other
+    dh::msm_ws wsA{}, wsB{};
+    int rcw = msm_workspace(w, gA, n, 1, wsw, wsA);
+    if (!rcw) rcw = msm_workspace(w, gB, n, n_keys, wsw, wsB);
+    if (!rcw) rcw = msm_workspace(w, gA, n, 1, wsw, wsA);
+    if (rcw) return rcw;
+    HIP_TRY(T.run("auth_msm_sigs", [&] {
+      return dh::launch_msm28_set(g2, gA, iota, nullptr, nullptr, n, 1, w->r_scal.as<uint4>(), w->s28.as<uint32_t>(), wsA,
+                                  w->outA.as<uint32_t>(), st);
+    }));
+    HIP_TRY(T.run("auth_msm_hash_by_key", [&] {
+      return dh::launch_msm28_set(g2, gB, iota, nullptr, w->a_kidx.as<uint32_t>(), n, n_keys, w->r_scal.as<uint4>(),
+                                  w->q28.as<uint32_t>(), wsB, w->outB.as<uint32_t>(), st);
+    }));
+    const size_t npairs = n_keys + 1;
+    HIP_TRY(w->r_P.ensure(npairs * JAC_WORDS_G1 * 4));
+    HIP_TRY(w->r_Q.ensure(npairs * JAC_WORDS_G2 * 4));
+    HIP_TRY(w->r_f.ensure(npairs * 192 * 4));
+    HIP_TRY(w->r_skip.ensure(npairs + 4));
+    HIP_TRY(w->pass.ensure(16));
+    HIP_TRY(T.run("auth_pair_check", [&] {
+      hipError_t e = dh::launch_recover_pairs(g2, w->a_shares.as<uint32_t>(), w->outB.as<uint32_t>(), w->outA.as<uint32_t>(),
+                                              (int)n_keys, w->r_P.as<uint32_t>(), w->r_Q.as<uint32_t>(), st);
+      if (e != hipSuccess) return e;
+      if (lane_pairing())
+        return dh::launch_pair_check(w->r_P.as<uint32_t>(), w->r_Q.as<uint32_t>(), npairs, 0, 0, nullptr, w->r_f.as<uint32_t>(),
+                                     w->r_skip.as<uint8_t>(), w->pass.as<uint8_t>(), st);
+      if ((e = w->vm_pairs.ensure(npairs * 72 * 4)) != hipSuccess) return e;
+      if ((e = w->vm_live.ensure(npairs)) != hipSuccess) return e;
+      return dh::launch_multi_pairing_vm(w->r_P.as<uint32_t>(), w->r_Q.as<uint32_t>(), npairs, w->vm_pairs.as<uint32_t>(),
+                                         w->vm_live.as<uint8_t>(), w->r_f.as<uint32_t>(), w->pass.as<uint8_t>(), st);
+    }));
+    uint8_t pass = 0;
+    HIP_TRY(hipMemcpyAsync(&pass, w->pass.p, 1, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    levels = 1;
+    // every item that decoded is valid when its key's check passed; the leaves below overwrite the others
+    HIP_TRY(dh::launch_ok_from_status(w->r_pstatus.as<uint8_t>(), n, w->r_ok.as<uint8_t>(), st));
+    if (pass != 1) {
+      std::vector<uint8_t> failing(n_keys, 1);
+      if (keys_used > 1) {
+        // level 2: A_k = the signature sum of key k's items (the hash MSM's grouping and geometry), then the check
+        // e(pk_k, [h] B_k) = e(g, A_k) as a leaf over n_keys virtual items (A_k, B_k, key k). A_k at infinity: the
+        // key has no live item (every scalar 0), nothing to check
+        levels = 2;
+        HIP_TRY(w->a_Ak.ensure(n_keys * jw * 4));
+        HIP_TRY(w->a_Akbytes.ensure(n_keys * (size_t)sl));
+        HIP_TRY(w->a_Akaff.ensure(n_keys * aw * 4 + 16));
+        HIP_TRY(w->a_Akstat.ensure(n_keys + 4));
+        HIP_TRY(w->a_kpass.ensure(n_keys + 4));
+        HIP_TRY(T.run("auth_msm_sigs_by_key", [&] {
+          return dh::launch_msm28_set(g2, gB, iota, nullptr, w->a_kidx.as<uint32_t>(), n, n_keys, w->r_scal.as<uint4>(),
+                                      w->s28.as<uint32_t>(), wsB, w->a_Ak.as<uint32_t>(), st);
+        }));
+        HIP_TRY(dh::launch_compress(g2, w->a_Ak.as<uint32_t>(), n_keys, w->a_Akbytes.as<uint8_t>(), w->a_Akaff.as<uint32_t>(),
+                                    w->a_Akstat.as<uint8_t>(), st));
+        HIP_TRY(hipMemsetAsync(w->a_kpass.p, 0, n_keys, st));
+        HIP_TRY(T.run("k_partial_leaf(auth keys)", [&] {
+          return dh::launch_partial_leaf(g2, iota, n_keys, w->a_Akaff.as<uint32_t>(), w->a_Akstat.as<uint8_t>(), iota, iota,
+                                         w->outB.as<uint32_t>(), w->a_shares.as<uint32_t>(), (int)n_keys,
+                                         w->a_kpass.as<uint8_t>(), st);
+        }));
+        std::vector<uint8_t> kpass(n_keys), akstat(n_keys);
+        HIP_TRY(hipMemcpyAsync(kpass.data(), w->a_kpass.p, n_keys, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(akstat.data(), w->a_Akstat.p, n_keys, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        size_t nf = 0;
+        for (size_t k = 0; k < n_keys; k++) nf += failing[k] = akstat[k] == 1 && kpass[k] != 1;
+        // the product failed yet every key's own check passed: only possible through a sum at infinity; check them all
+        if (!nf) failing.assign(n_keys, 1);
+      }
+      // level 3: leaf checks for the items under failing keys
+      levels = 3;
+      std::vector<uint32_t> list;
+      std::vector<uint8_t> seen(n_keys, 0);
+      for (size_t i = 0; i < n; i++)
+        if (failing[kidx[i]]) {
+          list.push_back((uint32_t)i);
+          if (!seen[kidx[i]]) seen[kidx[i]] = 1, keys_failed++;
+        }
+      HIP_TRY(w->a_list.ensure(list.size() * 4 + 4));
+      HIP_TRY(hipMemcpyAsync(w->a_list.p, list.data(), list.size() * 4, hipMemcpyHostToDevice, st));
+      HIP_TRY(leaves(w->a_list.as<uint32_t>(), list.size()));
+      leaf_items = list.size();
+      HIP_TRY(hipStreamSynchronize(st));  // list is read by the copy above
+    }
+  }
+  std::vector<uint8_t> kst(n_keys);
+  HIP_TRY(hipMemcpyAsync(verdict_out, w->r_ok.p, n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(kst.data(), w->a_kstatus.p, n_keys, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint64_t rejected = 0;
+  for (size_t i = 0; i < n; i++) rejected += verdict_out[i] != 1;
+  if (key_ok_out)
+    for (size_t k = 0; k < n_keys; k++) key_ok_out[k] = kst[k] == 1 ? 1 : 0;
+  if (stats) {
+    stats[0] = levels;
+    stats[1] = keys_failed;
+    stats[2] = leaf_items;
+    stats[3] = rejected;
+  }
+  return DH_OK;
+}
+
 // ---- one call over several internal streams (the drop-in callers make ONE call per window)
 // Off by default: measured on the MI355X (profiles/split_sweep_r02k_*.jsonl), one stream per call is the fastest
 // form of a call (1M rounds 64.9 ms, 4M 225.8 ms = 92% of the 8-batches-in-flight rate) — a chunk's per-round
@@ -2073,6 +2358,62 @@ int dh_verify_partials_batch(int scheme, const uint8_t* commits, int t, int n_no
   std::vector<uint8_t> status(n_rounds);
   return recover_core(L.w, scheme, commits, t, n_nodes, msgs32, partials, part_off, n_rounds, nullptr, status.data(),
                       L.w->stream, ok_out);
+}
+
+int dh_bls_verify_batch(int scheme, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx, const uint8_t* msgs,
+                        const uint32_t* msg_off, const uint8_t* sigs, size_t sig_stride, size_t n, uint8_t* verdict_out,
+                        uint8_t* key_ok_out, uint64_t seed, uint64_t stats_out[4]) {
+  if (scheme < 0 || scheme > 3) return fail(DH_EINVAL, "unknown scheme %d", scheme);
+  const bool g2 = sig_on_g2(scheme);
+  const size_t sl = g2 ? 96 : 48;
+  if (stats_out) memset(stats_out, 0, 4 * sizeof(uint64_t));
+  if (n_keys && !keys) return fail(DH_EINVAL, "null key table");
+  if (!key_idx && n_keys != n) return fail(DH_EINVAL, "key_idx is null: one key per item, yet %zu keys for %zu items", n_keys, n);
+  if (n && !n_keys) return fail(DH_EINVAL, "%zu items and no keys", n);
+  if (n && (!msg_off || !sigs || !verdict_out)) return fail(DH_EINVAL, "null argument");
+  if (sig_stride < sl || sig_stride % 4) return fail(DH_EINVAL, "bad signature stride %zu", sig_stride);
+  // entries of the MSM's sorted list keep a sign bit and address parts * n points; the key table feeds int-sized kernels
+  if (n >= ((size_t)1 << 31) / (g2 ? 4 : 2) || n_keys > ((size_t)1 << 24)) return fail(DH_EINVAL, "batch too large");
+  std::vector<uint32_t> kidx(n), off(n + 1, 0);
+  std::vector<uint8_t> used(n_keys, 0);
+  size_t keys_used = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (msg_off[i + 1] < msg_off[i]) return fail(DH_EINVAL, "msg_off must be non-decreasing");
+    const uint32_t k = key_idx ? key_idx[i] : (uint32_t)i;
+    if (k >= n_keys) return fail(DH_EINVAL, "item %zu: key index %u outside the table of %zu keys", i, k, n_keys);
+    kidx[i] = k;
+    off[i + 1] = msg_off[i + 1] - msg_off[0];
+    if (!used[k]) used[k] = 1, keys_used++;
+  }
+  if (off[n] && !msgs) return fail(DH_EINVAL, "null messages");
+  if (n == 0) return DH_OK;
+  lease L;
+  if (L.rc) return L.rc;
+  int rc = set_device_and_stream(L.w);
+  if (rc) return rc;
+  rc = auth_core(L.w, scheme, keys, n_keys, kidx.data(), keys_used, msgs ? msgs + msg_off[0] : nullptr, off.data(), sigs, sig_stride,
+                 n, verdict_out, key_ok_out, seed, stats_out, L.w->stream);
+  if (rc) (void)hipStreamSynchronize(L.w->stream);  // nothing of this call stays queued on the worker
+  return rc;
+}
+
+int dh_identity_hash_batch(int scheme, const uint8_t* keys, size_t n, uint8_t* out32) {
+  const int kl = dh_key_len(scheme);
+  if (kl < 0) return kl;
+  if (n && (!keys || !out32)) return fail(DH_EINVAL, "null argument");
+  for (size_t i = 0; i < n; i++) blake2b_256(keys + i * (size_t)kl, (size_t)kl, out32 + 32 * i);
+  return DH_OK;
+}
+
+int dh_identity_verify_batch(int scheme, const uint8_t* keys, const uint8_t* sigs, size_t sig_stride, size_t n,
+                             uint8_t* verdict_out) {
+  std::vector<uint8_t> msgs(n * 32);
+  std::vector<uint32_t> off(n + 1);
+  int rc = dh_identity_hash_batch(scheme, keys, n, msgs.data());
+  if (rc) return rc;
+  for (size_t i = 0; i <= n; i++) off[i] = (uint32_t)(32 * i);
+  return dh_bls_verify_batch(scheme, keys, n, nullptr, msgs.data(), off.data(), sigs, sig_stride, n, verdict_out, nullptr, 0,
+                             nullptr);
 }
 
 static void sk_words(const uint8_t* sk32, uint32_t w[8]) {

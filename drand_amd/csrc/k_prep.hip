@@ -268,6 +268,33 @@ __global__ __launch_bounds__(EXC_THREADS, 1) void k_add_iso_g2_exc(const uint32_
   }
 }
 
+// ---------------------------------------------------------------- prep: messages of any length (AuthScheme)
+// The same two kernels for message i = msgs[msg_off[i] .. msg_off[i + 1]) instead of a 32-byte digest (xmd_any,
+// sha256.hpp): kyber's sign/bls Verify hashes the message as given. Outputs as above: G1 the hash point before
+// cofactor clearing, G2 u0, u1 for the unchanged k_sswu_g2 / k_add_iso_g2 passes.
+__global__ __launch_bounds__(256, occ<fp>::W) void k_prep_msgv_g1(const uint8_t* __restrict__ msgs, const uint32_t* __restrict__ msg_off,
+                                                             size_t n, int dst_id, uint32_t* __restrict__ q_out) {
+  size_t i = gtid();
+  if (i >= n) return;
+  const uint32_t lo = msg_off[i];
+  uint32_t b[4][8];
+  xmd_any<4>(b, msgs + lo, msg_off[i + 1] - lo, dst_id);
+  st_jac_aos<fp>(q_out, i, h2c_g1_map(fp_from_be512(b[0], b[1]), fp_from_be512(b[2], b[3])));
+}
+
+__global__ __launch_bounds__(256) void k_h2fv_g2(const uint8_t* __restrict__ msgs, const uint32_t* __restrict__ msg_off, size_t n,
+                                                 int dst_id, uint32_t* __restrict__ u_out) {
+  size_t i = gtid();
+  if (i >= n) return;
+  const uint32_t lo = msg_off[i];
+  uint32_t b[8][8];
+  xmd_any<8>(b, msgs + lo, msg_off[i + 1] - lo, dst_id);
+  const fp2 u0 = {fp_from_be512(b[0], b[1]), fp_from_be512(b[2], b[3])};
+  const fp2 u1 = {fp_from_be512(b[4], b[5]), fp_from_be512(b[6], b[7])};
+  st_f<fp2>(u_out + 48 * i, u0);
+  st_f<fp2>(u_out + 48 * i + 24, u1);
+}
+
 // ---------------------------------------------------------------- RLC scalars
 // r_i = first 16 bytes of SHA-256(seed[32] || i_be64), 0 for rounds that failed decoding.
 __global__ __launch_bounds__(256) void k_scalars(const uint32_t* __restrict__ seed_words, size_t n,
@@ -377,6 +404,17 @@ hipError_t launch_decode_key(int key_g2, const uint8_t* pk, uint32_t* key_aff, u
 // G2: the SSWU points (2 x 72 words per round), then the exceptional-round list (count + n indices)
 size_t hash_tmp_bytes(int sig_g2, size_t n) { return sig_g2 ? n * 2 * 72 * 4 + (n + 1) * 4 : 0; }
 
+// G2 passes 2 and 3 over the u0, u1 that pass 1 left in q_out
+static hipError_t hash_g2_map(size_t n, uint32_t* q_out, uint32_t* tmp, hipStream_t st) {
+  hipLaunchKernelGGL(k_sswu_g2, dim3(nblk(2 * n, 256)), dim3(256), 0, st, (const uint32_t*)q_out, 2 * n, tmp);
+  uint32_t* exc = tmp + n * 2 * 72;
+  hipError_t e = hipMemsetAsync(exc, 0, 4, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_add_iso_g2, dim3(nblk(n, 256)), dim3(256), 0, st, (const uint32_t*)tmp, n, q_out, exc);
+  hipLaunchKernelGGL(k_add_iso_g2_exc, dim3(1), dim3(EXC_THREADS), 0, st, (const uint32_t*)tmp, (const uint32_t*)exc, q_out);
+  return hipGetLastError();
+}
+
 hipError_t launch_hash(int sig_g2, const uint64_t* rounds, const uint8_t* prevs, size_t prev_stride, const uint32_t* prev_lens,
                        const uint8_t* msgs32, size_t n, int chained, int dst_id, uint8_t* status, uint32_t* q_out, uint32_t* tmp,
                        hipStream_t st) {
@@ -389,13 +427,18 @@ hipError_t launch_hash(int sig_g2, const uint64_t* rounds, const uint8_t* prevs,
   // u0, u1 of round i go to q_out (48 of its 72 words per round), the SSWU points to tmp
   hipLaunchKernelGGL(k_h2f_g2, dim3(nblk(n, 256)), dim3(256), 0, st, rounds, prevs, prev_stride, prev_lens, msgs32, n, chained,
                      dst_id, status, q_out);
-  hipLaunchKernelGGL(k_sswu_g2, dim3(nblk(2 * n, 256)), dim3(256), 0, st, (const uint32_t*)q_out, 2 * n, tmp);
-  uint32_t* exc = tmp + n * 2 * 72;
-  hipError_t e = hipMemsetAsync(exc, 0, 4, st);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_add_iso_g2, dim3(nblk(n, 256)), dim3(256), 0, st, (const uint32_t*)tmp, n, q_out, exc);
-  hipLaunchKernelGGL(k_add_iso_g2_exc, dim3(1), dim3(EXC_THREADS), 0, st, (const uint32_t*)tmp, (const uint32_t*)exc, q_out);
-  return hipGetLastError();
+  return hash_g2_map(n, q_out, tmp, st);
+}
+
+hipError_t launch_hash_var(int sig_g2, const uint8_t* msgs, const uint32_t* msg_off, size_t n, int dst_id, uint32_t* q_out,
+                           uint32_t* tmp, hipStream_t st) {
+  if (!n) return hipSuccess;
+  if (!sig_g2) {
+    hipLaunchKernelGGL(k_prep_msgv_g1, dim3(nblk(n, 256)), dim3(256), 0, st, msgs, msg_off, n, dst_id, q_out);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(k_h2fv_g2, dim3(nblk(n, 256)), dim3(256), 0, st, msgs, msg_off, n, dst_id, q_out);
+  return hash_g2_map(n, q_out, tmp, st);
 }
 
 DH_COUNTER_ACCESSOR(prep)

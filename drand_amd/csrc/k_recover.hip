@@ -662,7 +662,41 @@ __global__ __launch_bounds__(64) void k_recover_pairs(const uint32_t* __restrict
   }
 }
 
+// ---------------------------------------------------------------- batch sign.Scheme.Verify under many keys
+// The caller's key table in the layout the pair and leaf kernels read public shares in (k_pubpoly_eval's: one
+// Jacobian key-group point per key): the affine keys k_prep_sig decoded and subgroup-tested, one lane per key; a key
+// that did not decode is the identity, which the pair kernels skip.
+template <class K>
+__global__ __launch_bounds__(256) void k_key_shares(const uint32_t* __restrict__ key_aff, const uint8_t* __restrict__ kstatus,
+                                                    size_t n_keys, uint32_t* __restrict__ out) {
+  size_t k = gtid();
+  if (k >= n_keys) return;
+  st_jac_aos<K>(out, k, kstatus[k] == DEC_OK ? jac_from_aff(ld_aff_aos<K>(key_aff, k)) : jac_inf<K>());
+}
+
+// an item under a key that did not decode is rejected like one whose signature did not: zero RLC scalar, verdict 0
+// (key_idx[i] < n_keys: checked on the host)
+__global__ __launch_bounds__(256) void k_mark_bad_key(const uint32_t* __restrict__ key_idx, size_t n,
+                                                      const uint8_t* __restrict__ kstatus, uint8_t* __restrict__ status) {
+  size_t i = gtid();
+  if (i < n && kstatus[key_idx[i]] != DEC_OK) status[i] = DEC_BAD;
+}
+
 // ---------------------------------------------------------------- launchers
+hipError_t launch_key_shares(int key_g2, const uint32_t* key_aff, const uint8_t* kstatus, size_t n_keys, uint32_t* out,
+                             hipStream_t st) {
+  if (!n_keys) return hipSuccess;
+  if (key_g2) hipLaunchKernelGGL(k_key_shares<fp2>, dim3(nblk(n_keys, 256)), dim3(256), 0, st, key_aff, kstatus, n_keys, out);
+  else hipLaunchKernelGGL(k_key_shares<fp>, dim3(nblk(n_keys, 256)), dim3(256), 0, st, key_aff, kstatus, n_keys, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_mark_bad_key(const uint32_t* key_idx, size_t n, const uint8_t* kstatus, uint8_t* status, hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(k_mark_bad_key, dim3(nblk(n, 256)), dim3(256), 0, st, key_idx, n, kstatus, status);
+  return hipGetLastError();
+}
+
 hipError_t launch_repack_partials(const uint8_t* raw, size_t n, int sig_len, uint8_t* sigs, uint32_t* idx, hipStream_t st) {
   if (!n) return hipSuccess;
   hipLaunchKernelGGL(k_repack_partials, dim3(nblk(n, 256)), dim3(256), 0, st, raw, n, sig_len, sigs, idx);

@@ -82,6 +82,10 @@ size_t hash_tmp_bytes(int sig_g2, size_t n);
 hipError_t launch_hash(int sig_g2, const uint64_t* rounds, const uint8_t* prevs, size_t prev_stride, const uint32_t* prev_lens,
                        const uint8_t* msgs32, size_t n, int chained, int dst_id, uint8_t* status, uint32_t* q_out, uint32_t* tmp,
                        hipStream_t st);
+// the same hash points for messages of any length, message i = msgs[msg_off[i] .. msg_off[i + 1]) (sign.Scheme.Verify
+// in batch: xmd_any, sha256.hpp); tmp: hash_tmp_bytes(sig_g2, n)
+hipError_t launch_hash_var(int sig_g2, const uint8_t* msgs, const uint32_t* msg_off, size_t n, int dst_id, uint32_t* q_out,
+                           uint32_t* tmp, hipStream_t st);
 // RLC scalars from SHA-256(seed || i): 127-bit (glv = 0) or a pair of 63-bit halves (glv = 1, msm_geom.halves = 2);
 // 0 for rounds whose status is not DEC_OK (status null: every round gets its scalar)
 // parts: 1 = one 127-bit scalar, 2 = two 63-bit halves, 4 = four 31-bit parts (msm_geom halves)
@@ -199,6 +203,11 @@ hipError_t launch_compress(int sig_g2, const uint32_t* pts, size_t n, uint8_t* o
                            hipStream_t st);
 hipError_t launch_recover_pairs(int sig_g2, const uint32_t* shares, const uint32_t* B, const uint32_t* A, int n_nodes,
                                 uint32_t* P, uint32_t* Q, hipStream_t st);
+// batch Verify under many keys: the decoded key table (affine, launch_prep's status) as per-key Jacobian points in
+// launch_pubpoly_eval's layout (a bad key: the identity), and status[i] = DEC_BAD for the items under a bad key
+hipError_t launch_key_shares(int key_g2, const uint32_t* key_aff, const uint8_t* kstatus, size_t n_keys, uint32_t* out,
+                             hipStream_t st);
+hipError_t launch_mark_bad_key(const uint32_t* key_idx, size_t n, const uint8_t* kstatus, uint8_t* status, hipStream_t st);
 
 #ifdef DH_COUNT_PRODUCTS
 // counting build: field products executed since the last take, per translation unit (fp_mul28.hpp)

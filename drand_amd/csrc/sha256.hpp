@@ -200,27 +200,9 @@ DH_DEV sha_h sha256_bytes(const uint8_t* p, uint64_t len) {
   return s;
 }
 
-// expand_message_xmd(SHA-256, msg = 32-byte digest, DST = 43 bytes, len = 32*NOUT):
-// writes NOUT 32-byte blocks b_1..b_NOUT (as big-endian words) into out[NOUT][8].
-// dst_id 0 = G2 DST, 1 = G1 DST; len_id 0 = 128 bytes (hash to G1), 1 = 256 bytes (G2).
+// b_1..b_NOUT of expand_message_xmd from b_0: b_i = SHA-256((b_0 ^ b_{i-1}) || I2OSP(i, 1) || DST'), b_0 ^ 0 for i = 1
 template <int NOUT>
-DH_DEV void xmd32(uint32_t out[NOUT][8], const sha_h& msg, int dst_id) {
-  constexpr int len_id = NOUT == 4 ? 0 : 1;
-  static_assert(NOUT == 4 || NOUT == 8, "xmd shape");
-  sha_h b0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) b0.h[i] = cst::XMD_ZPAD_H[i];
-  {
-    uint32_t w[16];
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = msg.h[j];
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[8 + j] = cst::XMD_B0A[dst_id][len_id][j];
-    sha_compress(b0, w);
-#pragma unroll
-    for (int j = 0; j < 16; j++) w[j] = cst::XMD_B0B[dst_id][j];
-    sha_compress(b0, w);
-  }
+DH_DEV void xmd_blocks(uint32_t out[NOUT][8], const sha_h& b0, int dst_id) {
   uint32_t prev[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) prev[j] = 0;
@@ -243,6 +225,89 @@ DH_DEV void xmd32(uint32_t out[NOUT][8], const sha_h& msg, int dst_id) {
       out[i - 1][j] = bi.h[j];
     }
   }
+}
+
+// expand_message_xmd(SHA-256, msg = 32-byte digest, DST = 43 bytes, len = 32*NOUT):
+// writes NOUT 32-byte blocks b_1..b_NOUT (as big-endian words) into out[NOUT][8].
+// dst_id 0 = G2 DST, 1 = G1 DST; len_id 0 = 128 bytes (hash to G1), 1 = 256 bytes (G2).
+template <int NOUT>
+DH_DEV void xmd32(uint32_t out[NOUT][8], const sha_h& msg, int dst_id) {
+  constexpr int len_id = NOUT == 4 ? 0 : 1;
+  static_assert(NOUT == 4 || NOUT == 8, "xmd shape");
+  sha_h b0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) b0.h[i] = cst::XMD_ZPAD_H[i];
+  {
+    uint32_t w[16];
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[j] = msg.h[j];
+#pragma unroll
+    for (int j = 0; j < 8; j++) w[8 + j] = cst::XMD_B0A[dst_id][len_id][j];
+    sha_compress(b0, w);
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = cst::XMD_B0B[dst_id][j];
+    sha_compress(b0, w);
+  }
+  xmd_blocks<NOUT>(out, b0, dst_id);
+}
+
+// byte k < 44 of DST' = DST || I2OSP(43, 1), read back from the b_i blocks above: b_i's message is
+// (b_0 ^ b_{i-1}) [32 bytes] || i || DST', so DST' starts at byte 33 of XMD_BIA || XMD_BIB
+DH_DEV uint32_t xmd_dst_prime_byte(int dst_id, uint32_t k) {
+  const uint32_t pos = 33 + k;
+  const uint32_t w = pos < 64 ? cst::XMD_BIA[dst_id][(pos - 32) >> 2] : cst::XMD_BIB[dst_id][(pos - 64) >> 2];
+  return (w >> (8 * (3 - (pos & 3)))) & 0xffu;
+}
+
+// expand_message_xmd for a message of ANY length at msg (global memory, any alignment): kyber's sign/bls Verify hashes
+// whatever it is given (AuthScheme: crypto/schemes.go:102,143,183), not only 32-byte digests. b_0's preimage is
+// Z_pad [64] || msg [len] || I2OSP(32 NOUT, 2) || 0 || DST' [44], 111 + len bytes: it starts from the constant
+// midstate of the Z_pad block, the message streams through in 64-byte blocks, and the last len % 64 message bytes,
+// the 47-byte tail and SHA-256's own padding (one block when len % 64 <= 8, else two) are assembled in registers:
+// no scratch row per lane (k_h2c_generic's form). b_1..b_NOUT as in xmd32.
+template <int NOUT>
+DH_DEV void xmd_any(uint32_t out[NOUT][8], const uint8_t* __restrict__ msg, uint32_t len, int dst_id) {
+  static_assert(NOUT == 4 || NOUT == 8, "xmd shape");
+  sha_h b0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) b0.h[i] = cst::XMD_ZPAD_H[i];
+  const uint32_t nfull = len >> 6, r = len & 63u;
+#pragma unroll 1
+  for (uint32_t blk = 0; blk < nfull; blk++) {
+    uint32_t w[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) w[j] = ld_be32(msg + (size_t)blk * 64 + 4 * j);
+    sha_compress(b0, w);
+  }
+  const uint8_t* rest = msg + (size_t)nfull * 64;  // r bytes
+  const uint32_t tot = r + 47;                     // bytes ahead of the 0x80
+  const uint32_t ntail = r > 8 ? 2 : 1;            // r + 47 + 1 + 8 <= 64 exactly when r <= 8
+  const uint64_t bits = ((uint64_t)len + 111) * 8;
+#pragma unroll 1
+  for (uint32_t t = 0; t < ntail; t++) {
+    uint32_t w[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      uint32_t v = 0;
+#pragma unroll
+      for (int b = 0; b < 4; b++) {
+        const uint32_t pos = t * 64 + (uint32_t)(4 * j + b);
+        uint32_t byte = 0;
+        if (pos < r) byte = rest[pos];
+        else if (pos == r) byte = (uint32_t)(32 * NOUT) >> 8;
+        else if (pos == r + 1) byte = (uint32_t)(32 * NOUT) & 0xffu;
+        else if (pos == r + 2) byte = 0;
+        else if (pos < tot) byte = xmd_dst_prime_byte(dst_id, pos - r - 3);
+        else if (pos == tot) byte = 0x80u;
+        v = (v << 8) | byte;
+      }
+      if (t == ntail - 1 && j == 14) v = (uint32_t)(bits >> 32);
+      if (t == ntail - 1 && j == 15) v = (uint32_t)bits;
+      w[j] = v;
+    }
+    sha_compress(b0, w);
+  }
+  xmd_blocks<NOUT>(out, b0, dst_id);
 }
 
 }  // namespace dh

@@ -245,6 +245,62 @@ class Scheme:
             raise SchemeError("not enough good public shares")
         return sigs[0].tobytes()
 
+    # ---- AuthScheme (kyber sign/bls, crypto/schemes.go:102,143,183): plain BLS under many keys, any message length
+    def verify_signatures(self, keys, messages, signatures, key_index=None, seed=0, want_stats=False):
+        """sign.Scheme.Verify in batch: item i is checked under keys[key_index[i]] (keys[i] when key_index is None,
+        and then len(keys) == n) for messages[i], a byte string of any length. Returns (verdicts (n,) bool,
+        key_ok (len(keys),) bool); a key that does not decode fails its items, not the call. With want_stats also
+        the (levels, keys_failed, leaf_items, items_rejected) tuple of the call."""
+        keys = [bytes(k) for k in keys]
+        msgs = [bytes(m) for m in messages]
+        n = len(msgs)
+        if any(len(k) != self.key_len for k in keys):
+            raise SchemeError("keys must be %d bytes" % self.key_len)
+        sigs = np.ascontiguousarray(signatures, dtype=np.uint8).reshape(-1, self.sig_len) if n else np.zeros((0, self.sig_len), np.uint8)
+        if sigs.shape != (n, self.sig_len):
+            raise SchemeError("signatures must be (%d, %d)" % (n, self.sig_len))
+        kidx = None
+        if key_index is not None:
+            kidx = np.ascontiguousarray(key_index, dtype=np.uint32)
+            if kidx.shape != (n,):
+                raise SchemeError("key_index must give one key per item")
+        off = np.zeros(n + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(msgs) or b"\0", dtype=np.uint8).copy()
+        ktab = np.frombuffer(b"".join(keys) or b"\0", dtype=np.uint8).copy()
+        verdict = np.zeros(max(n, 1), dtype=np.uint8)
+        key_ok = np.zeros(max(len(keys), 1), dtype=np.uint8)
+        stats = np.zeros(4, dtype=np.uint64)
+        _check(_lib.load().dh_bls_verify_batch(self.id, _ptr(ktab), len(keys), _ptr(kidx), _ptr(blob), _ptr(off), _ptr(sigs),
+                                               self.sig_len, n, _ptr(verdict), _ptr(key_ok), int(seed), _ptr(stats)))
+        out = verdict[:n].astype(bool), key_ok[:len(keys)].astype(bool)
+        return out + (tuple(int(x) for x in stats),) if want_stats else out
+
+    def identity_hash(self, key):
+        """Identity.Hash (key/keys.go:53-57): BLAKE2b-256 of the compressed public key. Host only."""
+        key = bytes(key)
+        if len(key) != self.key_len:
+            raise SchemeError("keys must be %d bytes" % self.key_len)
+        out = np.zeros(32, dtype=np.uint8)
+        k = np.frombuffer(key, dtype=np.uint8).copy()
+        _check(_lib.load().dh_identity_hash_batch(self.id, _ptr(k), 1, _ptr(out)))
+        return out.tobytes()
+
+    def verify_identities(self, keys, signatures):
+        """Identity.ValidSignature for n identities in one call (the loop of Group.UnsignedIdentities,
+        key/group.go:487-495): (n,) bool, True where signatures[i] is keys[i]'s signature of identity_hash(keys[i])."""
+        keys = [bytes(k) for k in keys]
+        n = len(keys)
+        if any(len(k) != self.key_len for k in keys):
+            raise SchemeError("keys must be %d bytes" % self.key_len)
+        sigs = np.ascontiguousarray(signatures, dtype=np.uint8).reshape(-1, self.sig_len) if n else np.zeros((0, self.sig_len), np.uint8)
+        if sigs.shape != (n, self.sig_len):
+            raise SchemeError("signatures must be (%d, %d)" % (n, self.sig_len))
+        ktab = np.frombuffer(b"".join(keys) or b"\0", dtype=np.uint8).copy()
+        verdict = np.zeros(max(n, 1), dtype=np.uint8)
+        _check(_lib.load().dh_identity_verify_batch(self.id, _ptr(ktab), _ptr(sigs), self.sig_len, n, _ptr(verdict)))
+        return verdict[:n].astype(bool)
+
     def randomness(self, signatures):
         sigs = np.ascontiguousarray(signatures, dtype=np.uint8)
         out = np.zeros((len(sigs), 32), dtype=np.uint8)
@@ -323,6 +379,25 @@ class ThresholdScheme:
         if not ok[0]:
             raise SchemeError("share: not enough good public shares to reconstruct secret commitment")
         return out[0].tobytes()
+
+
+class AuthScheme:
+    """kyber sign.Scheme (sign/bls) over libdrandhip: the schemes' AuthScheme (crypto/schemes.go:102,143,183), in the
+    shape of the cgo type in INTEGRATION.md §2 (gpuAuthScheme). Verify runs on the device for a message of any length;
+    signing and key generation stay on the host (kyber): secret keys never reach the device."""
+
+    def __init__(self, scheme):
+        self.scheme = scheme
+
+    def verify(self, public, msg, sig):
+        """Verify(public, msg, sig): raises SchemeError("bls: invalid signature") unless sig is public's signature
+        of msg (a key or signature that does not decode fails the same way, as kyber's Verify returns an error)."""
+        s = self.scheme
+        if len(public) != s.key_len or len(sig) != s.sig_len:
+            raise SchemeError("bls: invalid signature")
+        verdicts, _ = s.verify_signatures([public], [msg], np.frombuffer(bytes(sig), dtype=np.uint8))
+        if not verdicts[0]:
+            raise SchemeError("bls: invalid signature")
 
 
 def _pack_prevs(previous_signatures, n):

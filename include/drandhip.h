@@ -15,6 +15,8 @@
  *   sign.ThresholdScheme.VerifyRecovered  [kyber v1.1.18 sign/tbls], called at crypto/schemes.go:71,
  *                                         chain/beacon/chainstore.go:207
  *   sign.ThresholdScheme.Recover          [kyber v1.1.18 sign/tbls], called at chain/beacon/chainstore.go:202
+ *   sign.Scheme.Verify (AuthScheme)       [kyber v1.1.18 sign/bls], crypto/schemes.go:102,143,183, called at
+ *                                         key/keys.go:61-64 (Identity.ValidSignature)
  * and adds the batch entry point the serial per-round loops need:
  *   chain/beacon/sync_manager.go:191-225 (CheckPastBeacons), client/verify.go:139-160, lp2p relays.
  * INTEGRATION.md shows the cgo binding a drand maintainer would add.
@@ -153,6 +155,40 @@ int dh_recover_batch(int scheme, const uint8_t* commits, int t, int n_nodes, con
  */
 int dh_verify_partials_batch(int scheme, const uint8_t* commits, int t, int n_nodes, const uint8_t* msgs32,
                              const uint8_t* partials, const uint32_t* part_off, size_t n_rounds, uint8_t* ok_out);
+
+/*
+ * sign.Scheme.Verify(public, msg, sig) in batch (kyber sign/bls Verify: the schemes' AuthScheme, crypto/schemes.go:102,
+ * 143,183, in the groups, hash and DST of the scheme's beacon signatures) under MANY keys and for messages of ANY
+ * length, 0 included: item i = key key_idx[i] of the table, message msgs[msg_off[i] .. msg_off[i+1]), signature i at
+ * sigs + i*sig_stride. Replaces per-item bls.Verify loops such as key/group.go:487-495 and the per-chain calls of a
+ * process that follows several chains of one scheme. Host buffers; blocks.
+ *   keys         n_keys compressed key-group points (dh_key_len bytes each); duplicates allowed
+ *   key_idx      n indices < n_keys (else DH_EINVAL); NULL = item i uses key i, and then n_keys must equal n
+ *   msg_off      n + 1 non-decreasing offsets into msgs (else DH_EINVAL)
+ *   verdict_out  n bytes: 1 exactly when Verify returns nil (signatures subgroup-checked, infinity rejected)
+ *   key_ok_out   n_keys bytes or NULL: 1 when the key decodes to a subgroup point (the rule of the group key of
+ *                dh_verify_batch). A bad key is not a call error: every item under it gets verdict 0, items under
+ *                other keys are unaffected
+ *   seed         as dh_verify_batch
+ *   stats_out    NULL or {levels, keys_failed, leaf_items, items_rejected}
+ * n = 0 is DH_OK and writes nothing; items with no keys are DH_EINVAL. The check: one product of n_keys + 1 pairings
+ * over random linear combinations per key; when it fails, one 2-pairing check per key, then per-item checks under
+ * the failing keys only; small batches and batches with few items per key go straight to per-item checks
+ * (DESIGN.md §10). DRANDHIP_AUTH_PATH=leaf|rlc (read at every call) forces per-item checks / the combined check.
+ */
+int dh_bls_verify_batch(int scheme, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx, const uint8_t* msgs,
+                        const uint32_t* msg_off, const uint8_t* sigs, size_t sig_stride, size_t n, uint8_t* verdict_out,
+                        uint8_t* key_ok_out, uint64_t seed, uint64_t stats_out[4]);
+
+/* Identity.Hash for n keys (key/keys.go:53-57): BLAKE2b-256 of each compressed key (dh_key_len bytes), host only, no
+ * device; out32: n*32 bytes */
+int dh_identity_hash_batch(int scheme, const uint8_t* keys, size_t n, uint8_t* out32);
+
+/* Identity.ValidSignature for n identities (key/keys.go:61-64; the serial loop of Group.UnsignedIdentities,
+ * key/group.go:487-495): verdict_out[i] = 1 when sigs[i] is key i's signature of Identity.Hash(key i), i.e.
+ * dh_bls_verify_batch over dh_identity_hash_batch with one key per item */
+int dh_identity_verify_batch(int scheme, const uint8_t* keys, const uint8_t* sigs, size_t sig_stride, size_t n,
+                             uint8_t* verdict_out);
 
 /*
  * Node-wide batch check over the GPUs of one node (one process per GPU; the sharded form of
