@@ -46,6 +46,8 @@ SIGNATURES = {
                                        _c.c_uint64, _P]),
     "dh_identity_hash_batch": (_c.c_int, [_c.c_int, _P, _c.c_size_t, _P]),
     "dh_identity_verify_batch": (_c.c_int, [_c.c_int, _P, _P, _c.c_size_t, _c.c_size_t, _P]),
+    "dh_schnorr_verify_batch": (_c.c_int, [_c.c_int, _P, _c.c_size_t, _P, _P, _P, _P, _c.c_size_t, _c.c_size_t, _P, _P]),
+    "dh_schnorr_sig_len": (_c.c_int, [_c.c_int]),
     "dh_sign_batch": (_c.c_int, [_c.c_int, _c.c_char_p, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P]),
     "dh_public_key": (_c.c_int, [_c.c_int, _c.c_char_p, _P]),
     "dh_partial_bytes": (_c.c_int, [_c.c_int]),

@@ -126,6 +126,8 @@ struct worker {
   // key indices and message offsets, the per-key signature sums (Jacobian, compressed, affine, status), the per-key
   // check results and the leaf list
   dbuf a_keys, a_kstatus, a_kaff, a_shares, a_kidx, a_moff, a_Ak, a_Akbytes, a_Akaff, a_Akstat, a_kpass, a_list;
+  // batch Schnorr verification (schnorr_core): the items' scalars and window digits, the per-key tables
+  dbuf s_sc, s_ktab;
   std::vector<uint8_t> h_verdict;
   // Recover: the (scheme, t, n_nodes, commits) whose decoded commits and public shares r_caff / r_shares hold
   std::vector<uint8_t> r_pub_key;
@@ -157,7 +159,7 @@ struct worker {
                    &r_e_sidx, &r_e_grp, &r_P, &r_Q, &r_f, &r_skip, &r_ok, &r_sel, &r_lam, &r_lamset, &r_rok, &r_sig,
                    &r_sigbytes, &r_status2, &r_aff2, &r_entries2, &r_off, &r_key, &r_den, &r_zs, &r_tbl, &r_rstat, &r_ltmp, &r_own, &r_need, &node_sum, &node_res,
                    &a_keys, &a_kstatus, &a_kaff, &a_shares, &a_kidx, &a_moff, &a_Ak, &a_Akbytes, &a_Akaff, &a_Akstat, &a_kpass,
-                   &a_list};
+                   &a_list, &s_sc, &s_ktab};
     for (dbuf* b : all) b->release();
     d_stage.release();
     sub_bad.release();
@@ -193,6 +195,13 @@ struct context {
   }();
   std::vector<worker*> pool;     // idle or leased workers
   std::vector<worker*> retired;  // leased when dh_shutdown ran: freed by their lease's end
+  // batch Schnorr verification: the table of odd multiples of each key group's generator ([0] G1, [1] G2), built by
+  // the first call that needs it and then read by every worker's check kernel. dh_shutdown drops them; while a call
+  // is still running they wait in gen_old for the next dh_shutdown that finds every worker idle.
+  std::mutex gen_mu;
+  dbuf gen_tab[2];
+  bool gen_ready[2] = {false, false};
+  std::vector<void*> gen_old;
 };
 context g_ctx;
 
@@ -604,7 +613,8 @@ static void prof_drain_locked() {
 static unsigned long long count_take_all() {
   unsigned long long t = 0, v = 0;
   hipError_t (*take[])(unsigned long long*) = {dh::count_take_prep, dh::count_take_msm, dh::count_take_check,
-                                               dh::count_take_sign, dh::count_take_recover, dh::count_take_vm};
+                                               dh::count_take_sign, dh::count_take_recover, dh::count_take_vm,
+                                               dh::count_take_schnorr};
   for (auto f : take)
     if (f(&v) == hipSuccess) t += v;
   return t;
@@ -1757,6 +1767,103 @@ int auth_core(worker* w, int scheme, const uint8_t* keys, size_t n_keys, const u
   return DH_OK;
 }
 
+// ---- schnorr.Verify in batch (dh_schnorr_verify_batch: the schemes' DKGAuthScheme, crypto/schemes.go:103,144,184;
+// dkg.VerifyPacketSignature, core/drand_beacon_control.go:354,476, and the leader's signature over group.Hash(),
+// core/group_setup.go:384). Per item [s]G == R + [h]P with h = SHA-512(R || P || msg) mod r: no
+// pairing and nothing shared between items but the tables, so the call is a fixed sequence of one-lane-per-item
+// kernels and one copy back. DRANDHIP_SCHNORR_PATH=plain, read at every call, takes the check from two plain
+// scalar multiplications instead of the joint chain over the tables.
+static bool schnorr_plain_env() {
+  const char* e = getenv("DRANDHIP_SCHNORR_PATH");
+  return e && !strcmp(e, "plain");
+}
+
+// the generator's table of the key group, built once per process (context::gen_tab)
+int schnorr_gen_table(bool key_g2, hipStream_t st, const uint32_t** out) {
+  std::lock_guard<std::mutex> lk(g_ctx.gen_mu);
+  const int g = key_g2 ? 1 : 0;
+  if (!g_ctx.gen_ready[g]) {
+    HIP_TRY(g_ctx.gen_tab[g].ensure(dh::schnorr_table_words(g) * 4));
+    HIP_TRY(dh::launch_schnorr_table(g, nullptr, nullptr, 1, 1, g_ctx.gen_tab[g].as<uint32_t>(), st));
+    HIP_TRY(hipStreamSynchronize(st));  // other workers' streams read it from now on
+    g_ctx.gen_ready[g] = true;
+  }
+  *out = g_ctx.gen_tab[g].as<uint32_t>();
+  return DH_OK;
+}
+
+// kidx: n key indices < n_keys (host); off: n + 1 message offsets from 0 (host)
+int schnorr_core(worker* w, int scheme, const uint8_t* keys, size_t n_keys, const uint32_t* kidx, const uint8_t* msgs,
+                 const uint32_t* off, const uint8_t* sigs, size_t sig_stride, size_t n, uint8_t* verdict_out,
+                 uint8_t* key_ok_out, hipStream_t st) {
+  const bool kg2 = !sig_on_g2(scheme);  // the key group is the other group of the beacon signatures
+  const size_t kl = kg2 ? 96 : 48;
+  const size_t kaw = (kg2 ? JAC_WORDS_G2 : JAC_WORDS_G1) * 2 / 3;
+  const size_t total = off[n];
+  const bool plain = schnorr_plain_env();
+  timed_launches T(st);
+  // 1. the key table: decode + subgroup test, one lane per key (dh_bls_verify_batch's rule)
+  HIP_TRY(w->a_keys.ensure(n_keys * kl + 4));
+  HIP_TRY(w->a_kstatus.ensure(n_keys + 4));
+  HIP_TRY(w->a_kaff.ensure(n_keys * kaw * 4 + 16));
+  HIP_TRY(hipMemcpyAsync(w->a_keys.p, keys, n_keys * kl, hipMemcpyHostToDevice, st));
+  HIP_TRY(T.run(kg2 ? "k_prep_sig<fp2>(schnorr keys)" : "k_prep_sig<fp>(schnorr keys)", [&] {
+    return dh::launch_prep(kg2, w->a_keys.as<uint8_t>(), kl, n_keys, w->a_kstatus.as<uint8_t>(), w->a_kaff.as<uint32_t>(), nullptr,
+                           st);
+  }));
+  // 2. R of every item: decoded to a curve point, no subgroup test; infinity and the items of a bad key rejected
+  HIP_TRY(w->r_raw.ensure(n * sig_stride + 4));
+  HIP_TRY(w->r_pstatus.ensure(n + 4));
+  HIP_TRY(w->r_paff.ensure(n * kaw * 4 + 16));
+  HIP_TRY(w->a_kidx.ensure(n * 4 + 4));
+  HIP_TRY(hipMemcpyAsync(w->r_raw.p, sigs, n * sig_stride, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w->a_kidx.p, kidx, n * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(T.run(kg2 ? "k_dec_sig_g2(schnorr R)" : "k_dec_sig_g1(schnorr R)", [&] {
+    return dh::launch_dec_sig(kg2, w->r_raw.as<uint8_t>(), sig_stride, n, w->r_pstatus.as<uint8_t>(), w->r_paff.as<uint32_t>(),
+                              nullptr, st);
+  }));
+  HIP_TRY(dh::launch_mark_bad_key(w->a_kidx.as<uint32_t>(), n, w->a_kstatus.as<uint8_t>(), w->r_pstatus.as<uint8_t>(), st));
+  // 3. s < r, the challenge and the window digits
+  HIP_TRY(w->r_msgs.ensure(total + 4));
+  HIP_TRY(w->a_moff.ensure((n + 1) * 4));
+  HIP_TRY(w->s_sc.ensure(n * dh::schnorr_scalar_words() * 4));
+  if (total) HIP_TRY(hipMemcpyAsync(w->r_msgs.p, msgs, total, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w->a_moff.p, off, (n + 1) * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(T.run("k_schnorr_scalars", [&] {
+    return dh::launch_schnorr_scalars(w->r_raw.as<uint8_t>(), sig_stride, (int)kl, w->a_keys.as<uint8_t>(), w->a_kidx.as<uint32_t>(),
+                                      w->r_msgs.as<uint8_t>(), w->a_moff.as<uint32_t>(), n, w->r_pstatus.as<uint8_t>(),
+                                      w->s_sc.as<uint32_t>(), st);
+  }));
+  // 4. the check
+  HIP_TRY(w->r_ok.ensure(n + 4));
+  if (plain) {
+    HIP_TRY(T.run(kg2 ? "k_schnorr_plain<fp2>" : "k_schnorr_plain<fp>", [&] {
+      return dh::launch_schnorr_plain(kg2, w->s_sc.as<uint32_t>(), w->r_pstatus.as<uint8_t>(), w->r_paff.as<uint32_t>(),
+                                      w->a_kidx.as<uint32_t>(), w->a_kaff.as<uint32_t>(), n, w->r_ok.as<uint8_t>(), st);
+    }));
+  } else {
+    const uint32_t* gtab = nullptr;
+    int rc = schnorr_gen_table(kg2, st, &gtab);
+    if (rc) return rc;
+    HIP_TRY(w->s_ktab.ensure(n_keys * dh::schnorr_table_words(kg2) * 4));
+    HIP_TRY(T.run(kg2 ? "k_schnorr_table<fp2>" : "k_schnorr_table<fp>", [&] {
+      return dh::launch_schnorr_table(kg2, w->a_kaff.as<uint32_t>(), w->a_kstatus.as<uint8_t>(), n_keys, 0,
+                                      w->s_ktab.as<uint32_t>(), st);
+    }));
+    HIP_TRY(T.run(kg2 ? "k_schnorr_check<fp2>" : "k_schnorr_check<fp>", [&] {
+      return dh::launch_schnorr_check(kg2, w->s_sc.as<uint32_t>(), w->r_pstatus.as<uint8_t>(), w->r_paff.as<uint32_t>(),
+                                      w->a_kidx.as<uint32_t>(), gtab, w->s_ktab.as<uint32_t>(), n, w->r_ok.as<uint8_t>(), st);
+    }));
+  }
+  std::vector<uint8_t> kst(key_ok_out ? n_keys : 0);
+  HIP_TRY(hipMemcpyAsync(verdict_out, w->r_ok.p, n, hipMemcpyDeviceToHost, st));
+  if (key_ok_out) HIP_TRY(hipMemcpyAsync(kst.data(), w->a_kstatus.p, n_keys, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (key_ok_out)
+    for (size_t k = 0; k < n_keys; k++) key_ok_out[k] = kst[k] == 1 ? 1 : 0;
+  return DH_OK;
+}
+
 // ---- one call over several internal streams (the drop-in callers make ONE call per window)
 // Off by default: measured on the MI355X (profiles/split_sweep_r02k_*.jsonl), one stream per call is the fastest
 // form of a call (1M rounds 64.9 ms, 4M 225.8 ms = 92% of the 8-batches-in-flight rate) — a chunk's per-round
@@ -1886,6 +1993,19 @@ void dh_shutdown(void) {
     }
     w->release_all();
     delete w;
+  }
+  {
+    std::lock_guard<std::mutex> gk(g_ctx.gen_mu);
+    for (int g = 0; g < 2; g++) {
+      if (g_ctx.gen_tab[g].p) g_ctx.gen_old.push_back(g_ctx.gen_tab[g].p);
+      g_ctx.gen_tab[g].p = nullptr;
+      g_ctx.gen_tab[g].cap = 0;
+      g_ctx.gen_ready[g] = false;
+    }
+    if (g_ctx.retired.empty()) {
+      for (void* q : g_ctx.gen_old) (void)hipFree(q);
+      g_ctx.gen_old.clear();
+    }
   }
   g_ctx.pool.clear();
   g_ctx.inited = false;
@@ -2393,6 +2513,42 @@ int dh_bls_verify_batch(int scheme, const uint8_t* keys, size_t n_keys, const ui
   if (rc) return rc;
   rc = auth_core(L.w, scheme, keys, n_keys, kidx.data(), keys_used, msgs ? msgs + msg_off[0] : nullptr, off.data(), sigs, sig_stride,
                  n, verdict_out, key_ok_out, seed, stats_out, L.w->stream);
+  if (rc) (void)hipStreamSynchronize(L.w->stream);  // nothing of this call stays queued on the worker
+  return rc;
+}
+
+int dh_schnorr_sig_len(int scheme) {
+  const int kl = dh_key_len(scheme);
+  return kl < 0 ? kl : kl + 32;
+}
+
+int dh_schnorr_verify_batch(int scheme, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx, const uint8_t* msgs,
+                            const uint32_t* msg_off, const uint8_t* sigs, size_t sig_stride, size_t n, uint8_t* verdict_out,
+                            uint8_t* key_ok_out) {
+  if (scheme < 0 || scheme > 3) return fail(DH_EINVAL, "unknown scheme %d", scheme);
+  const size_t sl = (size_t)dh_schnorr_sig_len(scheme);
+  if (n_keys && !keys) return fail(DH_EINVAL, "null key table");
+  if (!key_idx && n_keys != n) return fail(DH_EINVAL, "key_idx is null: one key per item, yet %zu keys for %zu items", n_keys, n);
+  if (n && !n_keys) return fail(DH_EINVAL, "%zu items and no keys", n);
+  if (n && (!msg_off || !sigs || !verdict_out)) return fail(DH_EINVAL, "null argument");
+  if (sig_stride < sl || sig_stride % 4) return fail(DH_EINVAL, "bad signature stride %zu", sig_stride);
+  if (n >= ((size_t)1 << 31) || n_keys > ((size_t)1 << 24)) return fail(DH_EINVAL, "batch too large");
+  std::vector<uint32_t> kidx(n), off(n + 1, 0);
+  for (size_t i = 0; i < n; i++) {
+    if (msg_off[i + 1] < msg_off[i]) return fail(DH_EINVAL, "msg_off must be non-decreasing");
+    const uint32_t k = key_idx ? key_idx[i] : (uint32_t)i;
+    if (k >= n_keys) return fail(DH_EINVAL, "item %zu: key index %u outside the table of %zu keys", i, k, n_keys);
+    kidx[i] = k;
+    off[i + 1] = msg_off[i + 1] - msg_off[0];
+  }
+  if (off[n] && !msgs) return fail(DH_EINVAL, "null messages");
+  if (n == 0) return DH_OK;
+  lease L;
+  if (L.rc) return L.rc;
+  int rc = set_device_and_stream(L.w);
+  if (rc) return rc;
+  rc = schnorr_core(L.w, scheme, keys, n_keys, kidx.data(), msgs ? msgs + msg_off[0] : nullptr, off.data(), sigs, sig_stride, n,
+                    verdict_out, key_ok_out, L.w->stream);
   if (rc) (void)hipStreamSynchronize(L.w->stream);  // nothing of this call stays queued on the worker
   return rc;
 }

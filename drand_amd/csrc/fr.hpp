@@ -80,6 +80,48 @@ DH_DEV fr fr_sub(const fr& a, const fr& b) {
   return r;
 }
 
+DH_DEV fr fr_add(const fr& a, const fr& b) {  // a, b < r
+  uint32_t t[8];
+  unsigned c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) t[i] = __builtin_addc(a.v[i], b.v[i], c, &c);
+  fr_sub_mod_if(t, c);
+  fr r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = t[i];
+  return r;
+}
+
+// w < r for little-endian words w (a scalar read from the wire: kyber's mod.Int.UnmarshalBinary refuses w >= r)
+DH_DEV bool fr_is_canonical(const uint32_t w[8]) {
+  unsigned br = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) (void)__builtin_subc(w[i], FR_MOD[i], br, &br);
+  return br != 0;
+}
+
+// A 512-bit big-endian integer d (16 words, d[0] the most significant: a SHA-512 digest) mod r, as canonical
+// little-endian words: the Schnorr challenge of DKGAuthScheme (kyber v1.1.18 sign/schnorr hash(): SetBytes of the
+// 64 digest bytes). d = hi 2^256 + lo. The Montgomery product takes any 256-bit operand beside one below r (its result
+// stays below 2r before the final subtraction), so lo R2 / R = lo R and hi R3 / R = hi 2^256 R (mod r, R = 2^256) are
+// one product each, their sum is d in Montgomery form and a product by 1 leaves d mod r.
+__device__ __constant__ uint32_t FR_R3[8] = {0x439b73afu, 0xc62c1807u, 0x8cf06990u, 0x1b3e0d18u,
+                                             0xc7b5f418u, 0x73d13c71u, 0xc8db33e9u, 0x6e2a5bb9u};  // 2^768 mod r
+DH_DEV void fr_from_be512(const uint32_t d[16], uint32_t out[8]) {
+  fr hi, lo, r2, r3, one;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    hi.v[i] = d[7 - i];
+    lo.v[i] = d[15 - i];
+    r2.v[i] = FR_R2[i];
+    r3.v[i] = FR_R3[i];
+    one.v[i] = i ? 0u : 1u;
+  }
+  const fr c = fr_mul(fr_add(fr_mul(hi, r3), fr_mul(lo, r2)), one);
+#pragma unroll
+  for (int i = 0; i < 8; i++) out[i] = c.v[i];
+}
+
 // Montgomery form of a small integer x < r
 DH_DEV fr fr_from_u32(uint32_t x) {
   fr a, r2;

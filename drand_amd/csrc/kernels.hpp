@@ -209,6 +209,25 @@ hipError_t launch_key_shares(int key_g2, const uint32_t* key_aff, const uint8_t*
                              hipStream_t st);
 hipError_t launch_mark_bad_key(const uint32_t* key_idx, size_t n, const uint8_t* kstatus, uint8_t* status, hipStream_t st);
 
+// batch Schnorr verification (k_schnorr.hip, DKGAuthScheme). status: n bytes from launch_dec_sig of R (without a
+// subgroup test) and launch_mark_bad_key. launch_schnorr_scalars rejects s >= r in status and writes, for the items
+// still DEC_OK, schnorr_scalar_words() words each: s, h = SHA-512(R || P || msg) mod r and the window digits of s and
+// -h. launch_schnorr_table: schnorr_table_words(key_g2) words per decoded key of the affine table (gen = 1: one table,
+// of the group's generator; key_aff and kstatus unused). launch_schnorr_check: verdict[i] = ([s]G - [h]P == R) from
+// the joint chain over the tables; launch_schnorr_plain: the same from two jac_mul_words on the affine keys.
+size_t schnorr_scalar_words();
+size_t schnorr_table_words(int key_g2);
+hipError_t launch_schnorr_scalars(const uint8_t* sigs, size_t stride, int key_len, const uint8_t* keys, const uint32_t* key_idx,
+                                  const uint8_t* msgs, const uint32_t* msg_off, size_t n, uint8_t* status, uint32_t* sc,
+                                  hipStream_t st);
+hipError_t launch_schnorr_table(int key_g2, const uint32_t* key_aff, const uint8_t* kstatus, size_t n_keys, int gen, uint32_t* tbl,
+                                hipStream_t st);
+hipError_t launch_schnorr_check(int key_g2, const uint32_t* sc, const uint8_t* status, const uint32_t* r_aff,
+                                const uint32_t* key_idx, const uint32_t* gtab, const uint32_t* ktabs, size_t n, uint8_t* verdict,
+                                hipStream_t st);
+hipError_t launch_schnorr_plain(int key_g2, const uint32_t* sc, const uint8_t* status, const uint32_t* r_aff,
+                                const uint32_t* key_idx, const uint32_t* key_aff, size_t n, uint8_t* verdict, hipStream_t st);
+
 #ifdef DH_COUNT_PRODUCTS
 // counting build: field products executed since the last take, per translation unit (fp_mul28.hpp)
 hipError_t count_take_prep(unsigned long long* v);
@@ -217,6 +236,7 @@ hipError_t count_take_check(unsigned long long* v);
 hipError_t count_take_sign(unsigned long long* v);
 hipError_t count_take_recover(unsigned long long* v);
 hipError_t count_take_vm(unsigned long long* v);
+hipError_t count_take_schnorr(unsigned long long* v);
 #endif
 
 }  // namespace dh

@@ -276,6 +276,42 @@ class Scheme:
         out = verdict[:n].astype(bool), key_ok[:len(keys)].astype(bool)
         return out + (tuple(int(x) for x in stats),) if want_stats else out
 
+    # ---- DKGAuthScheme (kyber sign/schnorr over the key group, crypto/schemes.go:103,144,184): the signatures on DKG
+    # deal / response / justification bundles and the leader's over group.Hash()
+    @property
+    def schnorr_sig_len(self):
+        """bytes of one Schnorr signature: R (a compressed key-group point) then s (32 bytes, big-endian)"""
+        return self.key_len + 32
+
+    def verify_dkg_signatures(self, keys, msgs, sigs, kidx=None, want_key_ok=False):
+        """schnorr.Verify in batch, shaped like verify_signatures: item i is checked under keys[kidx[i]] (keys[i] when
+        kidx is None, and then len(keys) == n) for msgs[i], a byte string of any length; sigs is (n, schnorr_sig_len)
+        uint8. Returns the (n,) bool verdicts, with want_key_ok also the (len(keys),) bool key_ok; a key that does not
+        decode fails its items, not the call. Signing stays with the caller (no secret reaches the device)."""
+        keys = [bytes(k) for k in keys]
+        msgs = [bytes(m) for m in msgs]
+        n, sl = len(msgs), self.schnorr_sig_len
+        if any(len(k) != self.key_len for k in keys):
+            raise SchemeError("keys must be %d bytes" % self.key_len)
+        sg = np.ascontiguousarray(sigs, dtype=np.uint8).reshape(-1, sl) if n else np.zeros((0, sl), np.uint8)
+        if sg.shape != (n, sl):
+            raise SchemeError("signatures must be (%d, %d)" % (n, sl))
+        ki = None
+        if kidx is not None:
+            ki = np.ascontiguousarray(kidx, dtype=np.uint32)
+            if ki.shape != (n,):
+                raise SchemeError("kidx must give one key per item")
+        off = np.zeros(n + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(msgs) or b"\0", dtype=np.uint8).copy()
+        ktab = np.frombuffer(b"".join(keys) or b"\0", dtype=np.uint8).copy()
+        verdict = np.zeros(max(n, 1), dtype=np.uint8)
+        key_ok = np.zeros(max(len(keys), 1), dtype=np.uint8)
+        _check(_lib.load().dh_schnorr_verify_batch(self.id, _ptr(ktab), len(keys), _ptr(ki), _ptr(blob), _ptr(off), _ptr(sg), sl,
+                                                   n, _ptr(verdict), _ptr(key_ok)))
+        v = verdict[:n].astype(bool)
+        return (v, key_ok[:len(keys)].astype(bool)) if want_key_ok else v
+
     def identity_hash(self, key):
         """Identity.Hash (key/keys.go:53-57): BLAKE2b-256 of the compressed public key. Host only."""
         key = bytes(key)

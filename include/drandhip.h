@@ -17,6 +17,8 @@
  *   sign.ThresholdScheme.Recover          [kyber v1.1.18 sign/tbls], called at chain/beacon/chainstore.go:202
  *   sign.Scheme.Verify (AuthScheme)       [kyber v1.1.18 sign/bls], crypto/schemes.go:102,143,183, called at
  *                                         key/keys.go:61-64 (Identity.ValidSignature)
+ *   sign.Scheme.Verify (DKGAuthScheme)    [kyber v1.1.18 sign/schnorr], crypto/schemes.go:103,144,184, called at
+ *                                         core/drand_beacon_control.go:354,476 and core/group_setup.go:384
  * and adds the batch entry point the serial per-round loops need:
  *   chain/beacon/sync_manager.go:191-225 (CheckPastBeacons), client/verify.go:139-160, lp2p relays.
  * INTEGRATION.md shows the cgo binding a drand maintainer would add.
@@ -189,6 +191,35 @@ int dh_identity_hash_batch(int scheme, const uint8_t* keys, size_t n, uint8_t* o
  * dh_bls_verify_batch over dh_identity_hash_batch with one key per item */
 int dh_identity_verify_batch(int scheme, const uint8_t* keys, const uint8_t* sigs, size_t sig_stride, size_t n,
                              uint8_t* verdict_out);
+
+/*
+ * schnorr.Verify(public, msg, sig) in batch: kyber's sign/schnorr over the scheme's key group, the schemes'
+ * DKGAuthScheme (crypto/schemes.go:103,144,184). It is what dkg.VerifyPacketSignature checks on every deal, response
+ * and justification bundle (core/drand_beacon_control.go:354,476) and what authenticates the leader's signature over
+ * group.Hash() (core/group_setup.go:384); the matching Sign (core/drand_beacon_control.go:1011) stays on the host.
+ * Items, keys and messages as dh_bls_verify_batch: item i = key key_idx[i] of the table, message
+ * msgs[msg_off[i] .. msg_off[i+1]) of any length, signature i at sigs + i*sig_stride. Host buffers; blocks;
+ * thread-safe. No reference vector exists for this scheme: the behaviour is the restatement in DESIGN.md §11.
+ *   sigs         dh_schnorr_sig_len bytes each: R, a compressed key-group point (dh_key_len bytes), then s, a 32-byte
+ *                big-endian integer. Verdict 0 when s >= r, when R does not decode (flags, x < p, on the curve) or is
+ *                the point at infinity. The last is a documented choice, like the index rule of
+ *                dh_verify_partials_batch above: kyber's behaviour for R at infinity is not pinned by any vector,
+ *                and no honest signer produces it. R is not subgroup-tested: [s]G - [h]P lies in the subgroup, so an
+ *                R outside it never satisfies the equation
+ *   verdict_out  n bytes: 1 exactly when [s]G == R + [h]P with h = SHA-512(R bytes || P bytes || msg) read as a
+ *                big-endian integer mod r, G the key group's generator and P the item's key
+ *   key_ok_out   n_keys bytes or NULL, the key rule of dh_bls_verify_batch: 1 when the key is a compressed subgroup
+ *                point other than infinity. A bad key is not a call error: its items get verdict 0
+ * DH_EINVAL: key_idx out of range, msg_off decreasing, key_idx NULL with n_keys != n, sig_stride below the signature
+ * length or not a multiple of 4, items but no keys. n = 0 is DH_OK and writes nothing. Each item is checked on its
+ * own (two scalar multiplications sharing one chain, no pairing). DRANDHIP_SCHNORR_PATH=plain (read at every call)
+ * selects the cross-check form, two plain double-and-add multiplications per item.
+ */
+int dh_schnorr_verify_batch(int scheme, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx, const uint8_t* msgs,
+                            const uint32_t* msg_off, const uint8_t* sigs, size_t sig_stride, size_t n, uint8_t* verdict_out,
+                            uint8_t* key_ok_out);
+/* bytes of one Schnorr signature: dh_key_len(scheme) + 32 */
+int dh_schnorr_sig_len(int scheme);
 
 /*
  * Node-wide batch check over the GPUs of one node (one process per GPU; the sharded form of
