@@ -38,13 +38,18 @@ def main():
         "msm_level0<fp2>": u["msm_level0"] + u.get("k_msm_prep28<fp2>", 0.0),
         "k_lagrange_t33": rec["k_lagrange"],
     }
+    # the batched G1 subgroup test: k_prep_sig<fp> is then the decode-only kernel's count, and the test of
+    # the bucket sums is counted per round of its batch
+    if "k_sub_batch_level0" in q:
+        units["k_sub_batch_level0"] = q["k_sub_batch_level0"]
     if rec_r is not None:  # random signer subsets: every round its own basis, the regular-window chains
         units["k_lagrange_t33_random"] = rec_r["k_lagrange"]
         units["k_wnaf_table_t33_random"] = rec_r.get("k_wnaf_table", 0.0)
     units["k_wnaf_table_t33"] = rec.get("k_wnaf_table", 0.0)
     wm["kernel_units_M_per_round"] = {k: round(v, 1) for k, v in units.items()}
     wm["executed_M_per_beacon"] = {
-        "g1_sig": round(units["k_prep_sig<fp>"] + units["k_prep_msg<fp>"] + units["msm_level0"], 1),
+        "g1_sig": round(units["k_prep_sig<fp>"] + units["k_prep_msg<fp>"] + units["msm_level0"]
+                        + units.get("k_sub_batch_level0", 0.0), 1),
         "g2_sig": round(units["k_prep_sig<fp2>"] + units["k_prep_msg<fp2>"] + units["msm_level0<fp2>"], 1),
     }
     wm["counts_source"] = os.path.relpath(src, os.path.dirname(HERE))
@@ -52,7 +57,10 @@ def main():
                          "round (bench/count_products.py on the counting build, 1,048,576-round batches; tbls at the "
                          "n = 64, t = 33 recover shape), one M = one Fp product or squaring = 300 mul32; the MSM's "
                          "count includes its point conversion (k_msm_prep28: lazy form, affine hash points, "
-                         "endomorphism images), poison tests, bucket reduction and window Horner")
+                         "endomorphism images), poison tests, bucket reduction and window Horner. Since r07 the G1 "
+                         "figures are those of a large local batch (batched subgroup test, DESIGN 12: k_prep_sig<fp> = "
+                         "the decode-only kernel, plus k_sub_batch_level0); node batches and batches below "
+                         "DRANDHIP_SUB_BATCH_MIN still run the fused kernel (1532.0 M per round, g1_sig 2922.4)")
     wm.pop("_doc_k_lagrange", None)
     with open(wm_path, "w") as f:
         json.dump(wm, f, indent=2)

@@ -116,6 +116,8 @@ struct worker {
   dbuf node_sum, node_res;
   // MSM
   dbuf cnt, off, scan_tmp, list, buckets, segs, outA, outB, out2, pass, part, meta;
+  // batched G1 subgroup test (verify_core): the bit-subset sums' scratch, and the result byte the host reads
+  dbuf sub_tmp, sub_pass;
   // lane-parallel pairing checks
   dbuf vm_pairs, vm_live, vm_done;
   // tbls Recover
@@ -148,6 +150,8 @@ struct worker {
   // fault density (faults per round) the last bisection of this worker observed at its first level: a replay's
   // consecutive windows fail alike, so a dense one starts its next bisection with smaller groups (next_group_size)
   double fault_density = 0;
+  // eligible batches this worker still sends through the fused subgroup test after a dense fallback (sub_backoff)
+  int sub_fused_left = 0;
   // set by dh_batch_begin while it queues a node batch on one stream (node_one_stream): no tail-stream handoff
   bool begin_one_stream = false;
   void release_all() {
@@ -159,7 +163,7 @@ struct worker {
                    &r_e_sidx, &r_e_grp, &r_P, &r_Q, &r_f, &r_skip, &r_ok, &r_sel, &r_lam, &r_lamset, &r_rok, &r_sig,
                    &r_sigbytes, &r_status2, &r_aff2, &r_entries2, &r_off, &r_key, &r_den, &r_zs, &r_tbl, &r_rstat, &r_ltmp, &r_own, &r_need, &node_sum, &node_res,
                    &a_keys, &a_kstatus, &a_kaff, &a_shares, &a_kidx, &a_moff, &a_Ak, &a_Akbytes, &a_Akaff, &a_Akstat, &a_kpass,
-                   &a_list, &s_sc, &s_ktab};
+                   &a_list, &s_sc, &s_ktab, &sub_tmp, &sub_pass};
     for (dbuf* b : all) b->release();
     d_stage.release();
     sub_bad.release();
@@ -855,8 +859,45 @@ struct prep_gate {
   std::function<void()> recorded;  // host side: `done` is recorded, the next chunk may queue behind it
 };
 
-// MSM workspace of one bisection level (m entries in ngroups groups of geometry g, Jacobian width jw words)
-static int msm_workspace(worker* w, const dh::msm_geom& g, size_t m, size_t ngroups, size_t jw, dh::msm_ws& ws) {
+// The batched G1 subgroup test: a large local batch of G1 signatures decodes without the per-round test
+// and tests the bit-subset sums of its level-0 sigma buckets instead. DRANDHIP_SUBGROUP_BATCH=0 keeps the fused
+// per-round test everywhere; DRANDHIP_SUB_BATCH_MIN is the smallest batch that takes the batched test. Its default,
+// 131,072 rounds, is the first size of the one-call sweep (profiles/r07/sub_batch_min_sweep.jsonl) at which the
+// batched path is not slower: the test is one wave's two [|u|] chains on the batch's latency path (1.2-1.8 ms), and
+// below ~100k rounds the fused kernel's per-round test costs one call less than that (4,096 rounds: 7.36 ms fused,
+// 7.72 batched; 65,536: 8.94 / 9.27; 131,072: 11.10 / 10.96; 1M: 45.7 / 34.2).
+static bool subgroup_batch_on() {
+  static const bool v = [] {
+    const char* e = getenv("DRANDHIP_SUBGROUP_BATCH");
+    return !(e && e[0] == '0');
+  }();
+  return v;
+}
+static size_t sub_batch_min() {
+  static const size_t v = [] {
+    const char* e = getenv("DRANDHIP_SUB_BATCH_MIN");
+    const long long d = e ? atoll(e) : 0;
+    return (size_t)(d >= 1 ? d : 131072);
+  }();
+  return v;
+}
+// A batch whose fallback flagged more than one round in 2000 (a replay over a store with corrupted signatures: the
+// windows that follow fail alike) sends the worker's next DRANDHIP_SUB_BACKOFF eligible batches (default 15) through
+// the fused kernel: such a batch pays the batched test, the exact test and one more MSM level, about 1.4x the fused
+// path (profiles/r07/faulted_quicknet_262144_no_backoff.jsonl); sparse faults (the odd bad round) do not start it.
+static int sub_backoff() {
+  static const int v = [] {
+    const char* e = getenv("DRANDHIP_SUB_BACKOFF");
+    const long d = e ? atol(e) : -1;
+    return (int)(d >= 0 && d <= 1 << 20 ? d : 15);
+  }();
+  return v;
+}
+
+// MSM workspace of one bisection level (m entries in ngroups groups of geometry g, Jacobian width jw words); sub: also
+// the batched subgroup test's scratch (ws.sub)
+static int msm_workspace(worker* w, const dh::msm_geom& g, size_t m, size_t ngroups, size_t jw, dh::msm_ws& ws,
+                         bool sub = false) {
   const size_t nk = ngroups * g.nwin * (size_t)g.nbuck;
   HIP_TRY(w->cnt.ensure(nk * 4));
   HIP_TRY(w->off.ensure((nk + 1) * 4));
@@ -874,6 +915,11 @@ static int msm_workspace(worker* w, const dh::msm_geom& g, size_t m, size_t ngro
   ws = dh::msm_ws{w->cnt.as<uint32_t>(), w->off.as<uint32_t>(), w->scan_tmp.as<uint32_t>(), w->list.as<uint32_t>(),
                   w->buckets.as<uint32_t>(), w->segs.as<uint32_t>(), w->out2.as<uint32_t>(), w->part.as<uint32_t>(),
                   w->meta.as<uint32_t>(), 0, (uint32_t*)((uint8_t*)w->segs.p + segs_bytes)};
+  if (sub) {
+    HIP_TRY(w->sub_tmp.ensure(dh::sub_batch_tmp_bytes(g)));
+    HIP_TRY(w->sub_pass.ensure(8));  // the result byte, and at byte 4 the fallback's count of flagged rounds
+    ws.sub = w->sub_tmp.as<uint32_t>();
+  }
   return DH_OK;
 }
 
@@ -909,6 +955,10 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
   // batch whose groups all pass clears the hint). Saves the level-0 MSM and pairing check per dense window.
   // (with a fixed ladder, DRANDHIP_BISECT, its first size)
   const bool skip0 = mode == VM_FULL && w->fault_density > 1.0 / 2000 && n > 4096 && skip_level0();
+  // the batched subgroup test: G1 signatures, a local batch with its own level 0, large enough (sub_batch_min)
+  const bool sub_eligible = !g2 && mode == VM_FULL && !skip0 && n >= 2 && n >= sub_batch_min() && subgroup_batch_on();
+  const bool sub_batch = sub_eligible && w->sub_fused_left == 0;
+  if (sub_eligible && w->sub_fused_left > 0) w->sub_fused_left--;  // after a dense fallback (sub_backoff)
   dh::msm_geom g0{};
   dh::msm_ws ws0{};
   if (mode <= VM_BEGIN) {
@@ -938,13 +988,14 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
       HIP_TRY(dh::launch_iota(w->entries.as<uint32_t>(), n, ts));
       g0 = geom_for(n, parts);
       g0.half_stride = (uint32_t)n;
-      rc = msm_workspace(w, g0, n, 1, wsw, ws0);
+      rc = msm_workspace(w, g0, n, 1, wsw, ws0, sub_batch);
       if (rc) return rc;
       HIP_TRY(dh::launch_msm_sort(g0, w->entries.as<uint32_t>(), nullptr, nullptr, n, 1, w->scal.as<uint4>(), ws0, ts));
     }
     if (gate && gate->wait) HIP_TRY(hipStreamWaitEvent(st, gate->wait, 0));
     HIP_TRY(T.run(g2 ? "k_prep_sig<fp2>" : "k_prep_sig<fp>", [&] {
-      return dh::launch_prep(g2, d_sigs, sig_stride, n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), d_rand, st);
+      return dh::launch_prep(g2, d_sigs, sig_stride, n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), d_rand, st,
+                             sub_batch);
     }));
     // hash points: of the beacon digests, or of the given 32-byte messages (VerifyRecovered); a chained record
     // longer than its slot rejects its round (status)
@@ -1018,7 +1069,7 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
     if (pre) {
       ws = ws0;
     } else {
-      const int rc = msm_workspace(w, g, m, ngroups, wsw, ws);
+      const int rc = msm_workspace(w, g, m, ngroups, wsw, ws, level == 0 && sub_batch);
       if (rc) return rc;
     }
     if (!(level == 0 && mode >= VM_FINISH)) {  // a resumed batch has its level-0 sums from dh_batch_begin
@@ -1038,6 +1089,14 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
                            st, w->key_cur + 48);
       }));
     }
+    // level 0 of a batch that decoded without the per-round subgroup test: the test of the sigma buckets' bit-subset
+    // sums, ANDed into the group's pass before the marking and the compaction below read it
+    const bool sub0 = level == 0 && sub_batch;
+    if (sub0) {
+      HIP_TRY(T.run("k_sub_batch_level0", [&] {
+        return dh::launch_sub_batch(pre ? g0 : g, ws, w->pass.as<uint8_t>(), w->sub_pass.as<uint8_t>(), st);
+      }));
+    }
     HIP_TRY(dh::launch_mark_groups(w->entries.as<uint32_t>(), m, gsize, w->pass.as<uint8_t>(), w->status.as<uint8_t>(),
                                    d_verdict, st));
     // failing groups' entries compacted on the device; only the failing-group count and the last group's flag
@@ -1053,7 +1112,22 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
     uint8_t last_pass = 1;
     HIP_TRY(hipMemcpyAsync(&nfail32, w->crank.as<uint32_t>() + ngroups, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(&last_pass, w->pass.as<uint8_t>() + ngroups - 1, 1, hipMemcpyDeviceToHost, st));
+    uint8_t sub_pass = 1;
+    if (sub0) HIP_TRY(hipMemcpyAsync(&sub_pass, w->sub_pass.p, 1, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    if (!sub_pass) {
+      // some T is outside G1: the exact per-round test, before the next level's MSM. The flagged rounds become DEC_BAD
+      // as the fused kernel leaves them, the bisection's bucket passes and leaves skip them: the verdicts of the fused path
+      HIP_TRY(w->sub_bad.ensure(n));
+      HIP_TRY(T.run("k_sub_exact", [&] {
+        return dh::launch_sub_exact(n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), w->sub_bad.as<uint8_t>(),
+                                    (uint32_t*)((uint8_t*)w->sub_pass.p + 4), st);
+      }));
+      uint32_t nbad = 0;
+      HIP_TRY(hipMemcpyAsync(&nbad, (uint8_t*)w->sub_pass.p + 4, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      if ((double)nbad * 2000 > (double)n) w->sub_fused_left = sub_backoff();
+    }
     level++;
     const size_t nfail = nfail32;
     if (stats) stats[1] += nfail;

@@ -408,4 +408,33 @@ DH_DEV bool g1_in_subgroup28(LD ld) {
   return f28_zero(f28_add(f28_mul(y, z3), acc.y));                     // y: P.y Z^3 == -Y
 }
 
+// The same test of a Jacobian point T = (X, Y, Z) in the lazy form (the batched test's bucket sums, k_msm.hip): phi(T)
+// = (beta X, Y, Z) compared projectively with -[u^2] T; the identity passes (it is in G1). ld() returns T with bounds
+// (26, 18, 6) at most (a stored sum); it is called again for the final comparison. beta: the 28-bit Montgomery constant.
+// A torsion point of small order reaches infinity inside a chain (the exact addition sets the flag, the doublings
+// keep it, the next addition restarts from T), as in the affine test.
+template <class LD>
+DH_DEV bool g1_jac_in_subgroup28(LD ld, const f28& beta) {
+  j28 t = ld();
+  if (t.inf) return true;
+#pragma unroll 1
+  for (int chain = 0; chain < 2; chain++) {
+    j28 acc = t;
+#pragma unroll 1
+    for (int b = 62; b >= 0; b--) {
+      acc = j28_dbl<true>(acc);
+      if ((cst::U_ABS >> b) & 1) acc = j28_add(acc, t);
+    }
+    t = acc;  // (26, 18, 4): the last step is a doubling
+  }
+  if (t.inf) return false;  // phi(T) is finite
+  asm volatile("" ::: "memory");
+  const j28 p = ld();
+  const f28 za2 = f28_sqr(t.z), zp2 = f28_sqr(p.z);                    // < 2
+  const f28 lx = f28_mul(f28_mul(p.x, beta), za2), rx = f28_mul(t.x, zp2);
+  if (!f28_zero(f28_sub<2>(lx, rx))) return false;                     // x: beta X_T Z_a^2 == X_a Z_T^2
+  const f28 ly = f28_mul(p.y, f28_mul(za2, t.z)), ry = f28_mul(t.y, f28_mul(zp2, p.z));
+  return f28_zero(f28_add(ly, ry));                                    // y: Y_T Z_a^3 == -Y_a Z_T^3
+}
+
 }  // namespace dh

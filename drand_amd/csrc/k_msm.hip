@@ -1077,6 +1077,89 @@ hipError_t launch_msm28_set(int sig_g2, const msm_geom& g, const uint32_t* pidx,
   return hipMemcpyAsync(out, ws.out2, ngroups * (sig_g2 ? 72 : 36) * 4, hipMemcpyDeviceToDevice, st);
 }
 
+// ================================================================ the batched G1 subgroup test
+// The level-0 buckets of the sigma set, B[w][d] = the signed sum of the sigma_i and phi(sigma_i) whose digit in window
+// row w has |digit| = d, are summed once more by the bits of d: T[w][b] = sum over the d with bit b set of B[w][d],
+// nwin x c random-subset sums of the batch's signatures. When every T is in G1, every decoded signature is, except
+// with probability 2^-63 (the digits of a 63-bit half are an injective recoding of it, and each digit's sign and bits
+// are read off the tests). So the per-round test (two [|u|] chains per signature, fp28.hpp) leaves the
+// per-round kernel and nwin x c lanes run it once per batch. The masked row sum: the digits with bit b set are d_j =
+// ((j >> b) << (b + 1)) | 2^b | (j mod 2^b), j < 2^(c-2) (bit c - 1: only d = 2^(c-1)); a lane adds SUB_G consecutive
+// ones (every lane of a pair the same count, no idle half), the wave tree sums the lanes, k_msm_rowred28 the waves'
+// partials. c x 2^(c-2) additions per row (262k at c = 16) against the fold's ~2^c, on buckets that exist already.
+// An empty bucket is the identity and is never read, like the reduction's.
+constexpr uint32_t SUB_G = 8;
+DH_DEV uint32_t sub_digit(uint32_t j, uint32_t b) { return ((j >> b) << (b + 1)) | (1u << b) | (j & ((1u << b) - 1)); }
+template <class C, bool EXACT>
+DH_DEV typename C::P sub_run(const uint32_t* __restrict__ buckets, const uint32_t* __restrict__ off, size_t row0, uint32_t b,
+                             uint32_t j0, uint32_t j1) {
+  typename C::P acc = C::inf();
+#pragma unroll 1
+  for (uint32_t j = j0; j < j1; j++) {
+    const size_t k = row0 + sub_digit(j, b);
+    if (off[k + 1] != off[k]) acc = C::template add_mem<EXACT>(acc, buckets + (size_t)3 * C::EW * k);
+  }
+  return acc;
+}
+// lane t: pair (w, b) = t / lpp (lpp lanes per pair, a multiple of 64: a wave serves one pair), out[t / 64] = the
+// wave's partial sum
+template <class C>
+__global__ __launch_bounds__(256, C::OCC) void k_sub_bits28(const uint32_t* __restrict__ buckets, const uint32_t* __restrict__ off,
+                                                            msm_geom g, uint32_t lpp, uint32_t* __restrict__ out) {
+  __shared__ uint32_t buf[lds_words<C>() * 256];
+  const size_t t = gtid();
+  const size_t nlanes = (size_t)g.nwin * g.c * lpp;
+  typename C::P acc = C::inf();
+  if (t < nlanes) {
+    const uint32_t pair = (uint32_t)(t / lpp), w = pair / g.c, b = pair % g.c;
+    const uint32_t cnt = b + 1 == (uint32_t)g.c ? 1u : 1u << (g.c - 2);
+    const uint32_t j0 = min(cnt, (uint32_t)(t % lpp) * SUB_G), j1 = min(cnt, j0 + SUB_G);
+    const size_t row0 = (size_t)w * g.nbuck;
+    acc = sub_run<C, false>(buckets, off, row0, b, j0, j1);
+    if (C::poisoned(acc)) acc = sub_run<C, true>(buckets, off, row0, b, j0, j1);
+  }
+  acc = wave_tree<C>(acc, buf, 64);
+  if (t < nlanes && (t & 63) == 0) stj28<C>(out, t / 64, acc);
+}
+// one lane per T: fails -> the level-0 group fails (pass[0], read by the marking and compaction queued behind) and
+// sub_pass[0] = 0 (preset to 1), which the host reads with the level's counts
+__global__ __launch_bounds__(64) void k_sub_test28(const uint32_t* __restrict__ tpts, uint32_t npairs, uint8_t* __restrict__ pass,
+                                                   uint8_t* __restrict__ sub_pass) {
+  const size_t i = gtid();
+  if (i >= npairs) return;
+  if (!g1_jac_in_subgroup28([&] { return ldj28<c28_g1>(tpts, i); }, f28_c(BETA28))) {
+    pass[0] = 0;
+    sub_pass[0] = 0;
+  }
+}
+
+static uint32_t sub_lanes_per_pair(const msm_geom& g) {
+  const uint32_t cnt = 1u << (g.c - 2);
+  return ((cnt + SUB_G - 1) / SUB_G + 63) / 64 * 64;
+}
+// the wave partials (nwin x c x lpp / 64 points), then the nwin x c sums T
+size_t sub_batch_tmp_bytes(const msm_geom& g) {
+  const size_t npairs = (size_t)g.nwin * g.c;
+  return (npairs * (sub_lanes_per_pair(g) / 64) + npairs) * 3 * W28 * 4;
+}
+// after the level-0 launch_msm28 of one group of G1 signatures (g, ws: that launch's; ws.sub: sub_batch_tmp_bytes)
+hipError_t launch_sub_batch(const msm_geom& g, const msm_ws& ws, uint8_t* pass, uint8_t* sub_pass, hipStream_t st) {
+  using C = c28_g1;
+  if (g.c < 3 || !ws.sub) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(sub_pass, 1, 1, st);
+  if (e != hipSuccess) return e;
+  const uint32_t npairs = (uint32_t)g.nwin * g.c, lpp = sub_lanes_per_pair(g), parts = lpp / 64;
+  uint32_t* tpts = ws.sub + (size_t)npairs * parts * 3 * W28;
+  const size_t nlanes = (size_t)npairs * lpp;
+  const unsigned blk = few_waves_block(nlanes);
+  hipLaunchKernelGGL(k_sub_bits28<C>, dim3(nblk(nlanes, blk)), dim3(blk), 0, st, ws.buckets, ws.off, g, lpp, ws.sub);
+  uint32_t pspan = 1;
+  while (pspan < parts) pspan *= 2;
+  hipLaunchKernelGGL(k_msm_rowred28<C>, dim3(npairs), dim3(64), 0, st, ws.sub, parts, pspan, tpts);
+  hipLaunchKernelGGL(k_sub_test28, dim3(nblk(npairs, 64)), dim3(64), 0, st, tpts, npairs, pass, sub_pass);
+  return hipGetLastError();
+}
+
 // bisection: the entries of the failing groups, in order, on the device (groups are runs of gsize consecutive entries,
 // only the last one partial, so a failing group's entries land at rank(group) * gsize + their offset in the group)
 __global__ void k_fail_flags(const uint8_t* __restrict__ pass, size_t ngroups, uint32_t* __restrict__ flags) {

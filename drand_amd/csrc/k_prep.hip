@@ -3,6 +3,8 @@
 //
 // Path (one call of dh_verify_batch, see drandhip.cpp):
 //   k_prep_sig     decode + subgroup-check every signature, randomness = SHA-256(sig)    [A4a, A5]
+//                  (a large local G1 batch: decode only, k_dec_sig_g1_batch; its subgroup test runs once per batch
+//                  on the level-0 sigma buckets, k_msm.hip launch_sub_batch)
 //   k_prep_msg     DigestBeacon + hash_to_curve without cofactor clearing               [A2, A3, A4b]
 //   k_scalars      128-bit random-linear-combination scalars r_i = SHA-256(seed || i)   [batching, new]
 //   MSM (grouped Pippenger, shared sort for both point sets):
@@ -87,9 +89,8 @@ __global__ __launch_bounds__(256, 2) void k_sub_sig_g2(size_t n, uint8_t* __rest
 // as the decode finishes and runs beside the subgroup test, whose result is ANDed into the verdict at the end
 // (k_and_subgroup). A G1 round's decode is a fraction of k_prep_sig<fp> (one square root); the test (two [|u|] chains)
 // is the rest. The subgroup kernels write only sub_bad (the point and status stay as the pairing check reads them).
-__global__ __launch_bounds__(64) void k_dec_sig_g1(const uint8_t* __restrict__ sigs, size_t stride, size_t n,
-                                                   uint8_t* __restrict__ status, uint32_t* __restrict__ sig_aff,
-                                                   uint8_t* __restrict__ rand_out) {
+DH_DEV void dec_sig_g1(const uint8_t* __restrict__ sigs, size_t stride, size_t n, uint8_t* __restrict__ status,
+                       uint32_t* __restrict__ sig_aff, uint8_t* __restrict__ rand_out) {
   size_t i = gtid();
   if (i >= n) return;
   const uint8_t* s = sigs + i * stride;
@@ -104,10 +105,22 @@ __global__ __launch_bounds__(64) void k_dec_sig_g1(const uint8_t* __restrict__ s
   status[i] = st;
   st_aff_aos<fp>(sig_aff, i, a);
 }
+__global__ __launch_bounds__(64) void k_dec_sig_g1(const uint8_t* __restrict__ sigs, size_t stride, size_t n,
+                                                   uint8_t* __restrict__ status, uint32_t* __restrict__ sig_aff,
+                                                   uint8_t* __restrict__ rand_out) {
+  dec_sig_g1(sigs, stride, n, status, sig_aff, rand_out);
+}
+// the same decode for the large local batch whose subgroup test is batched (launch_prep defer_sub, k_msm.hip
+// launch_sub_batch): k_prep_sig<fp>'s blocks and occupancy, without its two [|u|] chains
+__global__ __launch_bounds__(256, occ<fp>::W) void k_dec_sig_g1_batch(const uint8_t* __restrict__ sigs, size_t stride, size_t n,
+                                                                      uint8_t* __restrict__ status, uint32_t* __restrict__ sig_aff,
+                                                                      uint8_t* __restrict__ rand_out) {
+  dec_sig_g1(sigs, stride, n, status, sig_aff, rand_out);
+}
 
 template <class F>
-__global__ __launch_bounds__(64) void k_sub_flag(size_t n, const uint8_t* __restrict__ status, const uint32_t* __restrict__ sig_aff,
-                                                 uint8_t* __restrict__ sub_bad) {
+DH_DEV void sub_flag(size_t n, const uint8_t* __restrict__ status, const uint32_t* __restrict__ sig_aff,
+                     uint8_t* __restrict__ sub_bad) {
   size_t i = gtid();
   if (i >= n) return;
   bool bad = false;
@@ -116,6 +129,26 @@ __global__ __launch_bounds__(64) void k_sub_flag(size_t n, const uint8_t* __rest
     else bad = !g2_in_subgroup28([&] { return ld_aff_aos<fp2>(sig_aff, i); });
   }
   sub_bad[i] = bad ? 1 : 0;
+}
+template <class F>
+__global__ __launch_bounds__(64) void k_sub_flag(size_t n, const uint8_t* __restrict__ status, const uint32_t* __restrict__ sig_aff,
+                                                 uint8_t* __restrict__ sub_bad) {
+  sub_flag<F>(n, status, sig_aff, sub_bad);
+}
+// the batched test's exact fallback over a whole batch (launch_sub_exact): k_prep_sig<fp>'s blocks and occupancy
+__global__ __launch_bounds__(256, occ<fp>::W) void k_sub_flag_batch(size_t n, const uint8_t* __restrict__ status,
+                                                                    const uint32_t* __restrict__ sig_aff,
+                                                                    uint8_t* __restrict__ sub_bad) {
+  sub_flag<fp>(n, status, sig_aff, sub_bad);
+}
+// a round the exact test flagged leaves as the fused k_prep_sig<fp> leaves it: DEC_BAD and the zero point
+__global__ __launch_bounds__(256) void k_sub_reject(size_t n, const uint8_t* __restrict__ sub_bad, uint8_t* __restrict__ status,
+                                                    uint32_t* __restrict__ sig_aff, uint32_t* __restrict__ nbad) {
+  size_t i = gtid();
+  if (i >= n || !sub_bad[i]) return;
+  atomicAdd(nbad, 1u);
+  status[i] = DEC_BAD;
+  st_aff_aos<fp>(sig_aff, i, aff<fp>{fp{}, fp{}});
 }
 
 __global__ __launch_bounds__(64) void k_and_subgroup(size_t n, const uint8_t* __restrict__ sub_bad, uint8_t* __restrict__ verdict) {
@@ -377,13 +410,25 @@ __global__ __launch_bounds__(128) void k_decode_key(const uint8_t* __restrict__ 
 
 
 hipError_t launch_prep(int sig_g2, const uint8_t* sigs, size_t stride, size_t n, uint8_t* status, uint32_t* sig_aff,
-                       uint8_t* rand_out, hipStream_t st) {
+                       uint8_t* rand_out, hipStream_t st, bool defer_sub) {
   if (!n) return hipSuccess;
   if (sig_g2) {
+    if (defer_sub) return hipErrorInvalidValue;  // G1 signatures only
     hipLaunchKernelGGL(k_dec_sig_g2, dim3(nblk(n, 256)), dim3(256), 0, st, sigs, stride, n, status, sig_aff, rand_out);
     hipLaunchKernelGGL(k_sub_sig_g2, dim3(nblk(n, 256)), dim3(256), 0, st, n, status, sig_aff);
-  } else
+  } else if (defer_sub)
+    hipLaunchKernelGGL(k_dec_sig_g1_batch, dim3(nblk(n, 256)), dim3(256), 0, st, sigs, stride, n, status, sig_aff, rand_out);
+  else
     hipLaunchKernelGGL(k_prep_sig<fp>, dim3(nblk(n, 256)), dim3(256), 0, st, sigs, stride, n, status, sig_aff, rand_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_sub_exact(size_t n, uint8_t* status, uint32_t* sig_aff, uint8_t* sub_bad, uint32_t* nbad, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(nbad, 0, 4, st);
+  if (e != hipSuccess || !n) return e;
+  hipLaunchKernelGGL(k_sub_flag_batch, dim3(nblk(n, 256)), dim3(256), 0, st, n, (const uint8_t*)status, (const uint32_t*)sig_aff,
+                     sub_bad);
+  hipLaunchKernelGGL(k_sub_reject, dim3(nblk(n, 256)), dim3(256), 0, st, n, (const uint8_t*)sub_bad, status, sig_aff, nbad);
   return hipGetLastError();
 }
 

@@ -40,6 +40,7 @@ struct msm_ws {
   uint32_t* meta;      // balanced bucket pass: 2 words per chunk (head kind, tail key)
   size_t max_entries;  // set by launch_msm_sort: upper bound of sorted-list entries (msm_entries)
   uint32_t* runs = nullptr;  // MSM28: the segments' running sums (as many points as segs)
+  uint32_t* sub = nullptr;   // batched G1 subgroup test (launch_sub_batch): sub_batch_tmp_bytes of scratch
 };
 
 // balanced bucket accumulation: entries per chunk, and workspace sizes for `max_entries` list entries
@@ -62,8 +63,14 @@ inline size_t msm_part_bytes(size_t max_entries, size_t jac_words, int nsets) {
 }
 inline size_t msm_meta_bytes(size_t max_entries) { return msm_nchunks(max_entries) * 2 * 4; }
 
+// defer_sub (G1 signatures): decode, curve check, randomness and status only; the subgroup test is left to the batch
+// (launch_sub_batch, or launch_sub_exact when that fails)
 hipError_t launch_prep(int sig_g2, const uint8_t* sigs, size_t stride, size_t n, uint8_t* status, uint32_t* sig_aff,
-                       uint8_t* rand_out, hipStream_t st);
+                       uint8_t* rand_out, hipStream_t st, bool defer_sub = false);
+// the exact fallback of the batched G1 subgroup test: the per-round test over the n decoded rounds (sub_bad: n bytes of
+// scratch); a failing round gets what the fused launch_prep leaves (status DEC_BAD, the zero point); *nbad (device
+// word) = the number of failing rounds
+hipError_t launch_sub_exact(size_t n, uint8_t* status, uint32_t* sig_aff, uint8_t* sub_bad, uint32_t* nbad, hipStream_t st);
 // small-batch path: the signature pass split at the decoded point (decode + randomness; subgroup test -> sub_bad[i]
 // = 1 when a decoded point is not in the subgroup; verdict[i] = 0 where sub_bad[i])
 hipError_t launch_dec_sig(int sig_g2, const uint8_t* sigs, size_t stride, size_t n, uint8_t* status, uint32_t* sig_aff,
@@ -106,6 +113,11 @@ hipError_t launch_msm28_set(int sig_g2, const msm_geom& g, const uint32_t* pidx,
 hipError_t launch_msm28(int sig_g2, const msm_geom& g, const uint32_t* entries, size_t m, size_t ngroups, const uint4* scal,
                         const uint32_t* S, const uint32_t* Q, msm_ws& ws, uint32_t* outA, uint32_t* outB, hipStream_t st,
                         const uint8_t* skip, bool presorted);
+// The batched G1 subgroup test on the sigma buckets a level-0 launch_msm28 of ONE group left in ws (g: that launch's
+// geometry; ws.sub: sub_batch_tmp_bytes(g)): the bit-subset sums T[w][b] of the buckets, each tested for membership.
+// A failing T clears pass[0] (the level-0 group) and sub_pass[0], which the launch first sets to 1.
+size_t sub_batch_tmp_bytes(const msm_geom& g);
+hipError_t launch_sub_batch(const msm_geom& g, const msm_ws& ws, uint8_t* pass, uint8_t* sub_pass, hipStream_t st);
 hipError_t launch_msm_sort(const msm_geom& g, const uint32_t* pidx, const uint32_t* sidx, const uint32_t* grp, size_t m,
                            size_t ngroups, const uint4* scal, msm_ws& ws, hipStream_t st);
 hipError_t launch_group_check(int sig_g2, const uint32_t* A, const uint32_t* B, size_t ngroups, const uint32_t* key_aff,
