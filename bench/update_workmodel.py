@@ -60,7 +60,10 @@ def main():
                          "endomorphism images), poison tests, bucket reduction and window Horner. Since r07 the G1 "
                          "figures are those of a large local batch (batched subgroup test, DESIGN 12: k_prep_sig<fp> = "
                          "the decode-only kernel, plus k_sub_batch_level0); node batches and batches below "
-                         "DRANDHIP_SUB_BATCH_MIN still run the fused kernel (1532.0 M per round, g1_sig 2922.4)")
+                         "DRANDHIP_SUB_BATCH_MIN still run the fused kernel (1532.0 M per round counted in r07, 1501.0 with the "
+                         "r08 square-root chain, which the decode-only kernel was counted to save: g1_sig 2831.4). r08: "
+                         "the fixed-exponent Fp chains run on a nine-entry dictionary (DESIGN 13): 78 products and 380 "
+                         "squarings per chain instead of 110-111 and 378")
     wm.pop("_doc_k_lagrange", None)
     with open(wm_path, "w") as f:
         json.dump(wm, f, indent=2)

@@ -325,11 +325,16 @@ DH_DEV fp fp_c(const uint32_t* c) {
 
 DH_DEV fp fp_mul_c(const fp& a, const uint32_t* c) { return fp_mul(a, fp_c(c)); }
 
-// x^e for a fixed exponent given as a sliding-window schedule (consts.hpp SCHED_*, w = 3):
-// table x, x^3, x^5, x^7; sched[0] = first table index, then (squarings << 8 | index), index 0xff =
-// squarings only. 378 squarings + ~105 multiplications for the 381-bit exponents (binary: ~228).
+// x^e for a fixed exponent given as a dictionary schedule (consts.hpp SCHED_*, gen_consts.py dict_schedule):
+// table x, x^3, ..., x^15 and the all-ones entry x^255 (the exponents have runs of 33, 19 and 17 ones); sched[0] =
+// first table index, then (squarings << 8 | index), index 0xff = squarings only. ~380 squarings + 76 products for
+// the 381-bit exponents (w = 3 in registers: 378 + 109; binary: ~228 products).
+// The table (SCHED_TAB x 56 bytes) does not fit in registers beside a product's working set at two waves per SIMD,
+// so it lives in per-lane scratch: every lane of a wave reads the same entry (the index comes from the wave-uniform
+// schedule), the load of a step's entry is issued BEFORE the step's squarings, which hide its latency, and the
+// entry occupies 14 VGPRs only from there to its product.
 // The chain runs on 14 x 28-bit limbs in Montgomery radix R' = 2^392 (fp_mul28.hpp mont_mul / mont_sqr, inlined):
-// x R enters as x R' by one product with 2^400 mod p and leaves by one product with 2^384 mod p, so the ~480
+// x R enters as x R' by one product with 2^400 mod p and leaves by one product with 2^384 mod p, so the ~460
 // products in between skip the 12 <-> 14 limb slicing and the final subtraction of the out-of-line bodies
 // (~110 of their ~610 instructions). Every intermediate value stays < 1.002 p with normalised limbs.
 struct fp28 {
@@ -369,25 +374,45 @@ DH_DEV fp fp28_to(const fp28& a) {  // x R' -> x R, canonical
   return o;
 }
 
-DH_DEV fp fp_pow_sched(const fp& x0, const uint32_t* sched, int len) {
-  const fp28 x = fp28_from(x0);
-  const fp28 x2 = fp28_sqr(x);
-  const fp28 t1 = fp28_mul(x, x2);
-  const fp28 t2 = fp28_mul(t1, x2);
-  const fp28 t3 = fp28_mul(t2, x2);
-  auto pick = [&](uint32_t k) { return k == 0 ? x : (k == 1 ? t1 : (k == 2 ? t2 : t3)); };
-  fp28 acc = pick(sched[0]);
+// the chain on a value already in the 28-bit form (x R', < 2p, normalised limbs), result in the same form
+DH_DEV fp28 fp28_pow_sched(const fp28& x, const uint32_t* sched, int len) {
+  fp28 tab[cst::SCHED_TAB];
+  {
+    const fp28 x2 = fp28_sqr(x);
+    fp28 t = x;
+    tab[0] = t;
+#pragma unroll 1
+    for (int k = 1; k < cst::SCHED_ODD; k++) {
+      t = fp28_mul(t, x2);
+      tab[k] = t;
+    }
+    // t = x^(2^r - 1), r = SCHED_W: each run entry doubles r
+#pragma unroll 1
+    for (int k = 0, r = cst::SCHED_W; k < cst::SCHED_RUNS; k++, r *= 2) {
+      const fp28 h = t;
+#pragma unroll 1
+      for (int j = 0; j < r; j++) t = fp28_sqr(t);
+      t = fp28_mul(t, h);
+      tab[cst::SCHED_ODD + k] = t;
+    }
+  }
+  fp28 acc = tab[sched[0]];
   uint32_t next = sched[1];  // the tables end with a 0 entry: the read one step ahead stays in bounds
 #pragma unroll 1
   for (int i = 1; i < len; i++) {
     const uint32_t op = next;
     next = sched[i + 1];  // scalar load issued a whole step before its use
     const uint32_t nsq = op >> 8, k = op & 0xff;
+    const fp28 e = tab[k == 0xff ? 0 : k];  // issued before the squarings
 #pragma unroll 1
     for (uint32_t j = 0; j < nsq; j++) acc = fp28_sqr(acc);
-    if (k != 0xff) acc = fp28_mul(acc, pick(k));
+    if (k != 0xff) acc = fp28_mul(acc, e);
   }
-  return fp28_to(acc);
+  return acc;
+}
+
+DH_DEV fp fp_pow_sched(const fp& x0, const uint32_t* sched, int len) {
+  return fp28_to(fp28_pow_sched(fp28_from(x0), sched, len));
 }
 
 DH_DEV fp fp_inv(const fp& x) { return fp_pow_sched(x, cst::SCHED_INV, cst::SCHED_INV_LEN); }

@@ -249,6 +249,87 @@ def window_schedule(e, wbits):
     return ops
 
 
+# The Fp chains' dictionary (fp.hpp fp28_pow_sched): the odd powers x^1 .. x^(2^SCHED_W - 1) (indices 0 ..
+# SCHED_ODD - 1) and SCHED_RUNS all-ones entries x^(2^r - 1), r = 2 SCHED_W, 4 SCHED_W, ... (each built from the
+# entry before it, which is x^(2^(r/2) - 1), by r/2 squarings and one product). The exponents have runs of 33, 19 and
+# 17 ones. Counted for (p + 1) / 4, the others within 0.4% (optimal parse, 392 MADs per product, 301 per squaring,
+# table build and the two domain conversions included): w = 3 111 products / 157.3 k MADs, w = 4 87 / 147.3 k,
+# w = 5 83 / 145.7 k, w = 4 with x^255 78 / 145.0 k (+4 squarings), w = 4 with x^255 and x^65535 75 / 146.2 k (+12).
+SCHED_W = 4
+SCHED_RUNS = 1
+MADS_MUL = 392
+MADS_SQR = 301
+
+
+def dict_words(wbits=SCHED_W, nruns=SCHED_RUNS):
+    """Exponents of the table entries, in table order."""
+    ws = [2 * i + 1 for i in range(1 << (wbits - 1))]
+    r = wbits
+    for _ in range(nruns):
+        r *= 2
+        ws.append((1 << r) - 1)
+    return ws
+
+
+def dict_schedule(e, wbits=SCHED_W, nruns=SCHED_RUNS):
+    """Cheapest left-to-right parse of e over dict_words (dynamic programme over bit positions: a 0 bit is a squaring,
+    a word of L bits is L squarings and a product; the first word costs no product and saves its squarings).
+    Same entry format as window_schedule: [first_index, (nsq << 8) | idx, ...], idx 0xff = squarings only."""
+    ws = [bin(d)[2:] for d in dict_words(wbits, nruns)]
+    b = bin(e)[2:]
+    n = len(b)
+    inf = float("inf")
+    cost = [inf] * (n + 1)
+    back = [None] * (n + 1)
+    for k, s in enumerate(ws):
+        if b.startswith(s) and -MADS_SQR * len(s) < cost[len(s)]:
+            cost[len(s)] = -MADS_SQR * len(s)
+            back[len(s)] = (None, k)
+    for i in range(1, n):
+        if cost[i] == inf:
+            continue
+        if b[i] == "0":
+            if cost[i] < cost[i + 1]:
+                cost[i + 1] = cost[i]
+                back[i + 1] = (i, None)
+            continue
+        for k, s in enumerate(ws):
+            if b.startswith(s, i) and cost[i] + MADS_MUL < cost[i + len(s)]:
+                cost[i + len(s)] = cost[i] + MADS_MUL
+                back[i + len(s)] = (i, k)
+    steps = []
+    i = n
+    while i is not None:
+        prev, k = back[i]
+        steps.append((prev, i, k))
+        i = prev
+    steps.reverse()
+    ops = [steps[0][2]]
+    acc = int(ws[steps[0][2]], 2)
+    pending = 0
+    for prev, i, k in steps[1:]:
+        pending += i - prev
+        if k is None:
+            continue
+        assert pending <= 255
+        ops.append((pending << 8) | k)
+        acc = (acc << pending) + int(ws[k], 2)
+        pending = 0
+    if pending:
+        assert pending <= 255
+        ops.append((pending << 8) | 0xFF)
+        acc <<= pending
+    assert acc == e
+    return ops
+
+
+def schedule_cost(ops, wbits=SCHED_W, nruns=SCHED_RUNS):
+    """(products, squarings) of one exponentiation in the 12 x 32-bit interface: table build, parse, two conversions."""
+    prods = (1 << (wbits - 1)) - 1 + nruns + sum(1 for op in ops[1:] if op & 0xFF != 0xFF) + 2
+    sqrs = 1 + sum(wbits << j for j in range(nruns)) + sum(op >> 8 for op in ops[1:])
+    return prods, sqrs
+
+
 def main():
     assert (P - 1) % 3 == 0 and P % 4 == 3
     xi = (1, 1)
@@ -352,11 +433,16 @@ def main():
         w("constexpr int %s_WORDS = %d;" % (name, n))
         w("constexpr int %s_BITS = %d;" % (name, e.bit_length()))
         w("__device__ __constant__ uint32_t %s[%d] = %s;" % (name, n, txt))
-    # sliding-window (w = 3, odd powers x^1,3,5,7) schedules for the fixed Fp exponents:
-    # entry = (squarings << 8) | table index, index 0xff = squarings only (trailing zeros)
+    # schedules for the fixed exponents: entry = (squarings << 8) | table index, index 0xff = squarings only (trailing
+    # zeros). Fp: the dictionary above (fp.hpp fp28_pow_sched); Fp2 (SCHED_SR2_C3, fp2.hpp fp2_pow_sched): sliding
+    # window, w = 3, odd powers x^1,3,5,7
+    w("constexpr int SCHED_W = %d;     // Fp chains: odd powers below 2^SCHED_W ..." % SCHED_W)
+    w("constexpr int SCHED_ODD = %d;   // ... at indices 0 .. SCHED_ODD - 1," % (1 << (SCHED_W - 1)))
+    w("constexpr int SCHED_RUNS = %d;  // then x^(2^(2 SCHED_W) - 1), x^(2^(4 SCHED_W) - 1), ..." % SCHED_RUNS)
+    w("constexpr int SCHED_TAB = %d;" % len(dict_words()))
     for name, e in (("SCHED_SQRT", (P + 1) // 4), ("SCHED_SR1_C1", sr1_c1), ("SCHED_INV", P - 2),
                     ("SCHED_LEGENDRE", (P - 1) // 2), ("SCHED_SR2_C3", c3)):
-        sched = window_schedule(e, 3)
+        sched = window_schedule(e, 3) if name == "SCHED_SR2_C3" else dict_schedule(e)
         w("constexpr int %s_LEN = %d;" % (name, len(sched)))
         # 32-bit entries: a wave-uniform index into a dword table is a scalar (s_load) read; 16-bit entries can only
         # be read by per-lane vector loads, whose latency each step of the chain then waits for
