@@ -859,7 +859,8 @@ struct prep_gate {
   std::function<void()> recorded;  // host side: `done` is recorded, the next chunk may queue behind it
 };
 
-// The batched G1 subgroup test: a large local batch of G1 signatures decodes without the per-round test
+// The batched subgroup test (G2: §14, below): a large local batch of G1 signatures decodes without the
+// per-round test
 // and tests the bit-subset sums of its level-0 sigma buckets instead. DRANDHIP_SUBGROUP_BATCH=0 keeps the fused
 // per-round test everywhere; DRANDHIP_SUB_BATCH_MIN is the smallest batch that takes the batched test. Its default,
 // 131,072 rounds, is the first size of the one-call sweep (profiles/r07/sub_batch_min_sweep.jsonl) at which the
@@ -881,6 +882,21 @@ static size_t sub_batch_min() {
   }();
   return v;
 }
+// The same for G2 signatures: an eligible batch runs its MSMs on two 63-bit psi halves instead of four
+// 31-bit parts (the claim needs the halves) and decodes without k_sub_sig_g2. DRANDHIP_SUB_BATCH_MIN_G2 is the
+// smallest such batch; DRANDHIP_SUB_BATCH_MIN stays the G1 minimum. Default: SUB_BATCH_MIN_G2_DEFAULT = 393,216
+// rounds, the first size of the one-call sweep (profiles/r09/sub_batch_g2_min_sweep.jsonl) from which the batched path
+// is not slower at every larger size: the two-half geometry has twice the window rows and the test is 2.8-5.5 ms on
+// the latency path (262,144 rounds: 30.5 ms fused, 30.8 batched; 393,216: 39.6-40.2 / 37.9; 1M: 84.4-84.9 / 69.8-70.0).
+constexpr size_t SUB_BATCH_MIN_G2_DEFAULT = 393216;
+static size_t sub_batch_min_g2() {
+  static const size_t v = [] {
+    const char* e = getenv("DRANDHIP_SUB_BATCH_MIN_G2");
+    const long long d = e ? atoll(e) : 0;
+    return (size_t)(d >= 1 ? d : SUB_BATCH_MIN_G2_DEFAULT);
+  }();
+  return v;
+}
 // A batch whose fallback flagged more than one round in 2000 (a replay over a store with corrupted signatures: the
 // windows that follow fail alike) sends the worker's next DRANDHIP_SUB_BACKOFF eligible batches (default 15) through
 // the fused kernel: such a batch pays the batched test, the exact test and one more MSM level, about 1.4x the fused
@@ -897,7 +913,7 @@ static int sub_backoff() {
 // MSM workspace of one bisection level (m entries in ngroups groups of geometry g, Jacobian width jw words); sub: also
 // the batched subgroup test's scratch (ws.sub)
 static int msm_workspace(worker* w, const dh::msm_geom& g, size_t m, size_t ngroups, size_t jw, dh::msm_ws& ws,
-                         bool sub = false) {
+                         bool sub = false, bool g2 = false) {
   const size_t nk = ngroups * g.nwin * (size_t)g.nbuck;
   HIP_TRY(w->cnt.ensure(nk * 4));
   HIP_TRY(w->off.ensure((nk + 1) * 4));
@@ -916,7 +932,7 @@ static int msm_workspace(worker* w, const dh::msm_geom& g, size_t m, size_t ngro
                   w->buckets.as<uint32_t>(), w->segs.as<uint32_t>(), w->out2.as<uint32_t>(), w->part.as<uint32_t>(),
                   w->meta.as<uint32_t>(), 0, (uint32_t*)((uint8_t*)w->segs.p + segs_bytes)};
   if (sub) {
-    HIP_TRY(w->sub_tmp.ensure(dh::sub_batch_tmp_bytes(g)));
+    HIP_TRY(w->sub_tmp.ensure(dh::sub_batch_tmp_bytes(g2, g)));
     HIP_TRY(w->sub_pass.ensure(8));  // the result byte, and at byte 4 the fallback's count of flagged rounds
     ws.sub = w->sub_tmp.as<uint32_t>();
   }
@@ -934,11 +950,9 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
   if (stats) memset(stats, 0, 4 * sizeof(uint64_t));
   if (n == 0) return DH_OK;
   // the MSM runs on lazily reduced 28-bit points (k_msm.hip MSM28), whose workspace points take 48 (G1) / 96 (G2)
-  // words; G2 splits each scalar in four psi parts, G1 in two endomorphism halves. (r01-r03 also kept a 12 x 32-bit
+  // words; G2 splits each scalar in four psi parts, G1 in two endomorphism halves; a G2 batch that takes the batched
+  // subgroup test runs on two 63-bit psi halves at every level (parts, below). (r01-r03 also kept a 12 x 32-bit
   // Pippenger behind DRANDHIP_MSM32 as a second implementation; removed in r04, git history has it.)
-  const int parts = g2 ? 4 : 2;
-  // sorted-list entries keep a sign bit and address parts * n points (the endomorphism images follow the n points)
-  if (n >= ((size_t)1 << 31) / parts) return fail(DH_EINVAL, "batch too large");
   const size_t jw = g2 ? JAC_WORDS_G2 : JAC_WORDS_G1;
   const size_t aw = jw * 2 / 3;
   const size_t wsw = g2 ? 96 : 48;
@@ -955,10 +969,16 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
   // batch whose groups all pass clears the hint). Saves the level-0 MSM and pairing check per dense window.
   // (with a fixed ladder, DRANDHIP_BISECT, its first size)
   const bool skip0 = mode == VM_FULL && w->fault_density > 1.0 / 2000 && n > 4096 && skip_level0();
-  // the batched subgroup test: G1 signatures, a local batch with its own level 0, large enough (sub_batch_min)
-  const bool sub_eligible = !g2 && mode == VM_FULL && !skip0 && n >= 2 && n >= sub_batch_min() && subgroup_batch_on();
+  // the batched subgroup test: a local batch with its own level 0, large enough (sub_batch_min, sub_batch_min_g2).
+  // Node batches (VM_BEGIN and the VM_FINISH modes resuming them) never take it, so both halves of such a batch
+  // compute the same parts.
+  const bool sub_eligible = mode == VM_FULL && !skip0 && n >= 2 && n >= (g2 ? sub_batch_min_g2() : sub_batch_min()) &&
+                            subgroup_batch_on();
   const bool sub_batch = sub_eligible && w->sub_fused_left == 0;
   if (sub_eligible && w->sub_fused_left > 0) w->sub_fused_left--;  // after a dense fallback (sub_backoff)
+  const int parts = g2 && !sub_batch ? 4 : 2;
+  // sorted-list entries keep a sign bit and address parts * n points (the endomorphism images follow the n points)
+  if (n >= ((size_t)1 << 31) / parts) return fail(DH_EINVAL, "batch too large");
   dh::msm_geom g0{};
   dh::msm_ws ws0{};
   if (mode <= VM_BEGIN) {
@@ -988,7 +1008,7 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
       HIP_TRY(dh::launch_iota(w->entries.as<uint32_t>(), n, ts));
       g0 = geom_for(n, parts);
       g0.half_stride = (uint32_t)n;
-      rc = msm_workspace(w, g0, n, 1, wsw, ws0, sub_batch);
+      rc = msm_workspace(w, g0, n, 1, wsw, ws0, sub_batch, g2);
       if (rc) return rc;
       HIP_TRY(dh::launch_msm_sort(g0, w->entries.as<uint32_t>(), nullptr, nullptr, n, 1, w->scal.as<uint4>(), ws0, ts));
     }
@@ -1013,7 +1033,7 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
     HIP_TRY(w->q28.ensure(parts * n * (g2 ? 64 : 32) * 4));
     HIP_TRY(T.run(g2 ? "k_msm_prep28<fp2>" : "k_msm_prep28<fp>", [&] {
       return dh::launch_msm_prep28(g2, n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(),
-                                   w->s28.as<uint32_t>(), w->q28.as<uint32_t>(), st);
+                                   w->s28.as<uint32_t>(), w->q28.as<uint32_t>(), st, 3, parts);
     }));
     HIP_TRY(hipMemsetAsync(d_verdict, 0, n, st));
     if (gate) {
@@ -1069,7 +1089,7 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
     if (pre) {
       ws = ws0;
     } else {
-      const int rc = msm_workspace(w, g, m, ngroups, wsw, ws, level == 0 && sub_batch);
+      const int rc = msm_workspace(w, g, m, ngroups, wsw, ws, level == 0 && sub_batch, g2);
       if (rc) return rc;
     }
     if (!(level == 0 && mode >= VM_FINISH)) {  // a resumed batch has its level-0 sums from dh_batch_begin
@@ -1094,7 +1114,7 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
     const bool sub0 = level == 0 && sub_batch;
     if (sub0) {
       HIP_TRY(T.run("k_sub_batch_level0", [&] {
-        return dh::launch_sub_batch(pre ? g0 : g, ws, w->pass.as<uint8_t>(), w->sub_pass.as<uint8_t>(), st);
+        return dh::launch_sub_batch(g2, pre ? g0 : g, ws, w->pass.as<uint8_t>(), w->sub_pass.as<uint8_t>(), st);
       }));
     }
     HIP_TRY(dh::launch_mark_groups(w->entries.as<uint32_t>(), m, gsize, w->pass.as<uint8_t>(), w->status.as<uint8_t>(),
@@ -1116,11 +1136,12 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
     if (sub0) HIP_TRY(hipMemcpyAsync(&sub_pass, w->sub_pass.p, 1, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (!sub_pass) {
-      // some T is outside G1: the exact per-round test, before the next level's MSM. The flagged rounds become DEC_BAD
-      // as the fused kernel leaves them, the bisection's bucket passes and leaves skip them: the verdicts of the fused path
+      // some T is outside the signature group: the exact per-round test, before the next level's MSM. The flagged rounds
+      // become DEC_BAD as the fused kernel leaves them, the bisection's bucket passes and leaves skip them: the verdicts
+      // of the fused path
       HIP_TRY(w->sub_bad.ensure(n));
       HIP_TRY(T.run("k_sub_exact", [&] {
-        return dh::launch_sub_exact(n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), w->sub_bad.as<uint8_t>(),
+        return dh::launch_sub_exact(g2, n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), w->sub_bad.as<uint8_t>(),
                                     (uint32_t*)((uint8_t*)w->sub_pass.p + 4), st);
       }));
       uint32_t nbad = 0;

@@ -277,4 +277,46 @@ DH_DEV bool g2_in_subgroup28(const aff<fp2>& p) {
   return g2_in_subgroup28([&] { return p; });
 }
 
+// The same test of a Jacobian point T = (X, Y, Z) in the lazy form (the batched test's bucket sums, k_msm.hip,
+// DESIGN §14): psi(T) = (conj(X) PSI_X, conj(Y) PSI_Y, conj(Z)) compared projectively with -[|u|] T; the identity
+// passes (it is in G2). ld() returns T as stored, with bounds (2, 3, 12) at most per component: every formula above
+// ends in X, Y < 2 and Z < 12, but a sum of ONE entry is that entry, and a bucket holding a single negated point keeps
+// the bucket pass's Y = 3p - y < 3 (f2_neg3) with Z = 1. The doubling and the addition accept Y < 3 (f2_sqr<3>, the
+// product bounds); the comparison conjugates Y with K = 3. ld() is called where the chain's five additions need T's coordinates and again for the
+// final comparison, so T is not live across the doublings. The chain runs with the fast additions first; an
+// exceptional case (a torsion point of small order reaching +-T or infinity inside the chain) leaves Z = 0 mod p,
+// which every later step keeps, and the poisoned result is recomputed with the exact additions (which set the
+// infinity flag, the doublings keep it, and the next addition restarts from T), as in g2_in_subgroup28.
+template <bool EXACT, class LD>
+DH_DEV j228 g2_jac_mul_uabs_ld(LD ld) {
+  auto q = [&](int k) { const j228 t = ld(); return k == 0 ? t.x : k == 1 ? t.y : t.z; };
+  j228 acc = ld();
+#pragma unroll 1
+  for (int r = 0; r < 6; r++) {
+    const int k = uabs_run(r);
+#pragma unroll 1
+    for (int i = 0; i < k; i++) acc = j228_dbl(acc);
+    if (r < 5) acc = j228_add_ld<EXACT>(acc, false, q);
+  }
+  return acc;
+}
+template <class LD>
+DH_DEV bool g2_jac_in_subgroup28(LD ld) {
+  if (ld().inf) return true;
+  j228 acc = g2_jac_mul_uabs_ld<false>(ld);
+  if (j228_poisoned(acc)) acc = g2_jac_mul_uabs_ld<true>(ld);
+  if (acc.inf) return false;  // psi(T) is finite
+  const j228 t = ld();
+  const f228 cz = {t.z.c0, f28_lin<12>(t.z.c1, -1, t.z.c1, 0)};          // conj(Z_T) < (12, 12)
+  const f228 za2 = f2_sqr<12>(acc.z), zt2 = f2_sqr<12>(cz);              // (2, 4)
+  const f228 px = f2_mul(f2_conj(t.x), f2_c28(PSI_X28));                 // (4, 6)
+  // x: psi(T).x Z_a^2 == X_a conj(Z_T)^2
+  if (!f2_zero(f2_lin<4, 6>(f2_mul(px, za2), 1, f2_mul(acc.x, zt2), -1))) return false;  // (8, 12)
+  const f228 cy = {t.y.c0, f28_lin<3>(t.y.c1, -1, t.y.c1, 0)};          // conj(Y_T), Y_T < 3
+  const f228 py = f2_mul(cy, f2_c28(PSI_Y28));                           // (4, 6)
+  const f228 ly = f2_mul(py, f2_mul(za2, acc.z));                        // Z_a^3: (4, 6) -> (4, 6)
+  const f228 ry = f2_mul(acc.y, f2_mul(zt2, cz));                        // conj(Z_T)^3: (4, 6) -> (4, 6)
+  return f2_zero(f2_add(ly, ry));                                        // y: psi(T).y Z_a^3 == -Y_a conj(Z_T)^3
+}
+
 }  // namespace dh

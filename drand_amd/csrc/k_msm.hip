@@ -408,6 +408,7 @@ DH_DEV void set_zero(f228& z) {
 // the lazy-form curve of each signature group: element / point types and the formulas the MSM needs
 struct c28_g1 {
   static constexpr int OCC = 2;  // waves per SIMD the bucket pass is compiled for
+  static constexpr bool IS_G2 = false;
   static constexpr int PARTS = 2;  // P, phi(P): two 63-bit scalar halves
   static constexpr size_t LCAP = 32;  // longest bucket-pass chunk
   using E = f28;
@@ -446,7 +447,10 @@ struct c28_g1 {
 };
 struct c28_g2 {
   static constexpr int OCC = 1;  // 512 registers: the G2 mixed addition's values fit VGPRs + AGPRs, no scratch
-  static constexpr int PARTS = 4;  // P, psi(P), psi^2(P), psi^3(P): four 31-bit scalar parts
+  static constexpr bool IS_G2 = true;
+  // P, psi(P), psi^2(P), psi^3(P): four 31-bit scalar parts; a batch that takes the batched subgroup test runs on
+  // P and psi(P) alone with two 63-bit halves, a property of the launch (msm_geom halves), not of the curve
+  static constexpr int PARTS = 4;
   static constexpr size_t LCAP = 64;
   using E = f228;
   using P = j228;
@@ -525,11 +529,13 @@ DH_DEV f28 c28_g1::endo_x(const f28& x) { return f28_mul(x, f28_c(BETA28)); }
 constexpr uint32_t PREP28_KMAX = 16;
 // the endomorphism images of affine point i at part * n + i
 template <class C>
-DH_DEV void prep28_images(uint32_t* __restrict__ out, size_t n, size_t i, const typename C::E& x, const typename C::E& y) {
+DH_DEV void prep28_images(uint32_t* __restrict__ out, size_t n, size_t i, const typename C::E& x, const typename C::E& y,
+                          uint32_t parts) {
   constexpr int EW = C::EW;
   st28(out + 2 * EW * (n + i), C::endo_x(x), 0);
   st28(out + 2 * EW * (n + i) + EW, C::endo_y(y), 0);
   if constexpr (C::PARTS == 4) {
+    if (parts != 4) return;  // two-half G2 batch: the arrays hold 2 n points
     const typename C::E x2 = C::psi2_x(x), y2 = C::psi2_y(y);
     st28(out + 2 * EW * (2 * n + i), x2, 0);
     st28(out + 2 * EW * (2 * n + i) + EW, y2, 0);
@@ -564,7 +570,8 @@ DH_DEV typename C::E block_product_scan(typename C::E v, typename C::E* sh) {
 template <class C>
 __global__ __launch_bounds__(256, 2) void k_msm_prep28(size_t n, uint32_t K, uint8_t* __restrict__ status,
                                                        const uint32_t* __restrict__ sig_aff, const uint32_t* __restrict__ q_pts,
-                                                       uint32_t* __restrict__ S, uint32_t* __restrict__ Q, uint32_t sets) {
+                                                       uint32_t* __restrict__ S, uint32_t* __restrict__ Q, uint32_t sets,
+                                                       uint32_t parts) {
   using E = typename C::E;
   using F = typename C::F;
   constexpr int EW = C::EW, FW = npw<F>::N;
@@ -578,7 +585,7 @@ __global__ __launch_bounds__(256, 2) void k_msm_prep28(size_t n, uint32_t K, uin
     const E x = C::in(a.x), y = C::in(a.y);
     st28(S + 2 * EW * i, x, 0);
     st28(S + 2 * EW * i + EW, y, 0);
-    prep28_images<C>(S, n, i, x, y);
+    prep28_images<C>(S, n, i, x, y, parts);
   }
   if (!(sets & 2)) return;  // a kernel argument: uniform, before the barriers
   E acc = C::one();
@@ -623,7 +630,7 @@ __global__ __launch_bounds__(256, 2) void k_msm_prep28(size_t n, uint32_t K, uin
     const E y = C::mulr(C::in(q.y), C::mulr(zi2, zi));
     st28(Q + 2 * EW * k, x, 0);
     st28(Q + 2 * EW * k + EW, y, 0);
-    prep28_images<C>(Q, n, k, x, y);
+    prep28_images<C>(Q, n, k, x, y, parts);
   }
 }
 
@@ -798,7 +805,7 @@ DH_DEV typename C::P lds_get_pt(const uint32_t* buf, int nthr, int i) {
 // a + the point in LDS slot i, its coordinates read where the formula uses them (G2: fewer values live)
 template <class C, bool EXACT>
 DH_DEV typename C::P add_lds(const typename C::P& a, const uint32_t* buf, int nthr, int i) {
-  if constexpr (C::PARTS == 4) {
+  if constexpr (C::IS_G2) {
     constexpr int EL = 28;
     f228 z;
     lds_get(buf, nthr, i, 2 * EL, z);
@@ -848,7 +855,7 @@ DH_DEV typename C::P wave_tree(typename C::P acc, uint32_t* buf, uint32_t span) 
     if ((lane & (2 * step - 1)) == 0) {
       typename C::P s = add_lds<C, false>(acc, buf, nthr, i + (int)step);
       if (C::poisoned(s)) {
-        if constexpr (C::PARTS == 4) s = add_lds_exact<C>(buf, nthr, i, i + (int)step);
+        if constexpr (C::IS_G2) s = add_lds_exact<C>(buf, nthr, i, i + (int)step);
         else s = add_lds<C, true>(lds_get_pt<C>(buf, nthr, i), buf, nthr, i + (int)step);  // G1: a call would cost
       }                                                                                        // the second wave/SIMD
       acc = s;
@@ -971,14 +978,18 @@ __global__ __launch_bounds__(64) void k_msm_windows28(const uint32_t* __restrict
 }
 
 hipError_t launch_msm_prep28(int sig_g2, size_t n, uint8_t* status, const uint32_t* sig_aff, const uint32_t* q_pts,
-                             uint32_t* S, uint32_t* Q, hipStream_t st, uint32_t sets) {
+                             uint32_t* S, uint32_t* Q, hipStream_t st, uint32_t sets, int parts) {
   if (!n) return hipSuccess;
+  if (parts == 0) parts = sig_g2 ? c28_g2::PARTS : c28_g1::PARTS;
+  if (parts != 2 && !(sig_g2 && parts == 4)) return hipErrorInvalidValue;
   const uint32_t K = prep28_k(n);
   const size_t nt = (n + K - 1) / K;
   if (sig_g2)
-    hipLaunchKernelGGL(k_msm_prep28<c28_g2>, dim3(nblk(nt, 256)), dim3(256), 0, st, n, K, status, sig_aff, q_pts, S, Q, sets);
+    hipLaunchKernelGGL(k_msm_prep28<c28_g2>, dim3(nblk(nt, 256)), dim3(256), 0, st, n, K, status, sig_aff, q_pts, S, Q, sets,
+                       (uint32_t)parts);
   else
-    hipLaunchKernelGGL(k_msm_prep28<c28_g1>, dim3(nblk(nt, 256)), dim3(256), 0, st, n, K, status, sig_aff, q_pts, S, Q, sets);
+    hipLaunchKernelGGL(k_msm_prep28<c28_g1>, dim3(nblk(nt, 256)), dim3(256), 0, st, n, K, status, sig_aff, q_pts, S, Q, sets,
+                       (uint32_t)parts);
   return hipGetLastError();
 }
 
@@ -1077,7 +1088,7 @@ hipError_t launch_msm28_set(int sig_g2, const msm_geom& g, const uint32_t* pidx,
   return hipMemcpyAsync(out, ws.out2, ngroups * (sig_g2 ? 72 : 36) * 4, hipMemcpyDeviceToDevice, st);
 }
 
-// ================================================================ the batched G1 subgroup test
+// ================================================================ the batched subgroup test (§14)
 // The level-0 buckets of the sigma set, B[w][d] = the signed sum of the sigma_i and phi(sigma_i) whose digit in window
 // row w has |digit| = d, are summed once more by the bits of d: T[w][b] = sum over the d with bit b set of B[w][d],
 // nwin x c random-subset sums of the batch's signatures. When every T is in G1, every decoded signature is, except
@@ -1123,11 +1134,15 @@ __global__ __launch_bounds__(256, C::OCC) void k_sub_bits28(const uint32_t* __re
 }
 // one lane per T: fails -> the level-0 group fails (pass[0], read by the marking and compaction queued behind) and
 // sub_pass[0] = 0 (preset to 1), which the host reads with the level's counts
+template <class C>
 __global__ __launch_bounds__(64) void k_sub_test28(const uint32_t* __restrict__ tpts, uint32_t npairs, uint8_t* __restrict__ pass,
                                                    uint8_t* __restrict__ sub_pass) {
   const size_t i = gtid();
   if (i >= npairs) return;
-  if (!g1_jac_in_subgroup28([&] { return ldj28<c28_g1>(tpts, i); }, f28_c(BETA28))) {
+  bool in;
+  if constexpr (C::IS_G2) in = g2_jac_in_subgroup28([&] { return ldj28<C>(tpts, i); });
+  else in = g1_jac_in_subgroup28([&] { return ldj28<C>(tpts, i); }, f28_c(BETA28));
+  if (!in) {
     pass[0] = 0;
     sub_pass[0] = 0;
   }
@@ -1138,26 +1153,30 @@ static uint32_t sub_lanes_per_pair(const msm_geom& g) {
   return ((cnt + SUB_G - 1) / SUB_G + 63) / 64 * 64;
 }
 // the wave partials (nwin x c x lpp / 64 points), then the nwin x c sums T
-size_t sub_batch_tmp_bytes(const msm_geom& g) {
+size_t sub_batch_tmp_bytes(int sig_g2, const msm_geom& g) {
   const size_t npairs = (size_t)g.nwin * g.c;
-  return (npairs * (sub_lanes_per_pair(g) / 64) + npairs) * 3 * W28 * 4;
+  return (npairs * (sub_lanes_per_pair(g) / 64) + npairs) * 3 * (sig_g2 ? c28_g2::EW : c28_g1::EW) * 4;
 }
-// after the level-0 launch_msm28 of one group of G1 signatures (g, ws: that launch's; ws.sub: sub_batch_tmp_bytes)
-hipError_t launch_sub_batch(const msm_geom& g, const msm_ws& ws, uint8_t* pass, uint8_t* sub_pass, hipStream_t st) {
-  using C = c28_g1;
-  if (g.c < 3 || !ws.sub) return hipErrorInvalidValue;
+// after the level-0 launch_msm28 of one group (g, ws: that launch's; ws.sub: sub_batch_tmp_bytes). G2: g.halves == 2
+// (the claim of DESIGN §14 is about two 63-bit halves; four 31-bit parts would bound the error by 2^-31 only)
+template <class C>
+static hipError_t sub_batch(const msm_geom& g, const msm_ws& ws, uint8_t* pass, uint8_t* sub_pass, hipStream_t st) {
+  if (g.c < 3 || g.halves != 2 || !ws.sub) return hipErrorInvalidValue;
   hipError_t e = hipMemsetAsync(sub_pass, 1, 1, st);
   if (e != hipSuccess) return e;
   const uint32_t npairs = (uint32_t)g.nwin * g.c, lpp = sub_lanes_per_pair(g), parts = lpp / 64;
-  uint32_t* tpts = ws.sub + (size_t)npairs * parts * 3 * W28;
+  uint32_t* tpts = ws.sub + (size_t)npairs * parts * 3 * C::EW;
   const size_t nlanes = (size_t)npairs * lpp;
   const unsigned blk = few_waves_block(nlanes);
   hipLaunchKernelGGL(k_sub_bits28<C>, dim3(nblk(nlanes, blk)), dim3(blk), 0, st, ws.buckets, ws.off, g, lpp, ws.sub);
   uint32_t pspan = 1;
   while (pspan < parts) pspan *= 2;
   hipLaunchKernelGGL(k_msm_rowred28<C>, dim3(npairs), dim3(64), 0, st, ws.sub, parts, pspan, tpts);
-  hipLaunchKernelGGL(k_sub_test28, dim3(nblk(npairs, 64)), dim3(64), 0, st, tpts, npairs, pass, sub_pass);
+  hipLaunchKernelGGL(k_sub_test28<C>, dim3(nblk(npairs, 64)), dim3(64), 0, st, tpts, npairs, pass, sub_pass);
   return hipGetLastError();
+}
+hipError_t launch_sub_batch(int sig_g2, const msm_geom& g, const msm_ws& ws, uint8_t* pass, uint8_t* sub_pass, hipStream_t st) {
+  return sig_g2 ? sub_batch<c28_g2>(g, ws, pass, sub_pass, st) : sub_batch<c28_g1>(g, ws, pass, sub_pass, st);
 }
 
 // bisection: the entries of the failing groups, in order, on the device (groups are runs of gsize consecutive entries,

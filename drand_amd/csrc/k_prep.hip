@@ -4,7 +4,8 @@
 // Path (one call of dh_verify_batch, see drandhip.cpp):
 //   k_prep_sig     decode + subgroup-check every signature, randomness = SHA-256(sig)    [A4a, A5]
 //                  (a large local G1 batch: decode only, k_dec_sig_g1_batch; its subgroup test runs once per batch
-//                  on the level-0 sigma buckets, k_msm.hip launch_sub_batch)
+//                  on the level-0 sigma buckets, k_msm.hip launch_sub_batch; a large local G2 batch
+//                  likewise: k_dec_sig_g2 without k_sub_sig_g2)
 //   k_prep_msg     DigestBeacon + hash_to_curve without cofactor clearing               [A2, A3, A4b]
 //   k_scalars      128-bit random-linear-combination scalars r_i = SHA-256(seed || i)   [batching, new]
 //   MSM (grouped Pippenger, shared sort for both point sets):
@@ -141,14 +142,21 @@ __global__ __launch_bounds__(256, occ<fp>::W) void k_sub_flag_batch(size_t n, co
                                                                     uint8_t* __restrict__ sub_bad) {
   sub_flag<fp>(n, status, sig_aff, sub_bad);
 }
-// a round the exact test flagged leaves as the fused k_prep_sig<fp> leaves it: DEC_BAD and the zero point
+// the G2 fallback: k_sub_sig_g2's blocks and occupancy
+__global__ __launch_bounds__(256, 2) void k_sub_flag_batch_g2(size_t n, const uint8_t* __restrict__ status,
+                                                              const uint32_t* __restrict__ sig_aff,
+                                                              uint8_t* __restrict__ sub_bad) {
+  sub_flag<fp2>(n, status, sig_aff, sub_bad);
+}
+// a round the exact test flagged leaves as the fused k_prep_sig<fp> / k_sub_sig_g2 leaves it: DEC_BAD and the zero point
+template <class F>
 __global__ __launch_bounds__(256) void k_sub_reject(size_t n, const uint8_t* __restrict__ sub_bad, uint8_t* __restrict__ status,
                                                     uint32_t* __restrict__ sig_aff, uint32_t* __restrict__ nbad) {
   size_t i = gtid();
   if (i >= n || !sub_bad[i]) return;
   atomicAdd(nbad, 1u);
   status[i] = DEC_BAD;
-  st_aff_aos<fp>(sig_aff, i, aff<fp>{fp{}, fp{}});
+  st_aff_aos<F>(sig_aff, i, aff<F>{F{}, F{}});
 }
 
 __global__ __launch_bounds__(64) void k_and_subgroup(size_t n, const uint8_t* __restrict__ sub_bad, uint8_t* __restrict__ verdict) {
@@ -413,9 +421,8 @@ hipError_t launch_prep(int sig_g2, const uint8_t* sigs, size_t stride, size_t n,
                        uint8_t* rand_out, hipStream_t st, bool defer_sub) {
   if (!n) return hipSuccess;
   if (sig_g2) {
-    if (defer_sub) return hipErrorInvalidValue;  // G1 signatures only
     hipLaunchKernelGGL(k_dec_sig_g2, dim3(nblk(n, 256)), dim3(256), 0, st, sigs, stride, n, status, sig_aff, rand_out);
-    hipLaunchKernelGGL(k_sub_sig_g2, dim3(nblk(n, 256)), dim3(256), 0, st, n, status, sig_aff);
+    if (!defer_sub) hipLaunchKernelGGL(k_sub_sig_g2, dim3(nblk(n, 256)), dim3(256), 0, st, n, status, sig_aff);
   } else if (defer_sub)
     hipLaunchKernelGGL(k_dec_sig_g1_batch, dim3(nblk(n, 256)), dim3(256), 0, st, sigs, stride, n, status, sig_aff, rand_out);
   else
@@ -423,12 +430,19 @@ hipError_t launch_prep(int sig_g2, const uint8_t* sigs, size_t stride, size_t n,
   return hipGetLastError();
 }
 
-hipError_t launch_sub_exact(size_t n, uint8_t* status, uint32_t* sig_aff, uint8_t* sub_bad, uint32_t* nbad, hipStream_t st) {
+hipError_t launch_sub_exact(int sig_g2, size_t n, uint8_t* status, uint32_t* sig_aff, uint8_t* sub_bad, uint32_t* nbad,
+                            hipStream_t st) {
   hipError_t e = hipMemsetAsync(nbad, 0, 4, st);
   if (e != hipSuccess || !n) return e;
+  if (sig_g2) {
+    hipLaunchKernelGGL(k_sub_flag_batch_g2, dim3(nblk(n, 256)), dim3(256), 0, st, n, (const uint8_t*)status,
+                       (const uint32_t*)sig_aff, sub_bad);
+    hipLaunchKernelGGL(k_sub_reject<fp2>, dim3(nblk(n, 256)), dim3(256), 0, st, n, (const uint8_t*)sub_bad, status, sig_aff, nbad);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(k_sub_flag_batch, dim3(nblk(n, 256)), dim3(256), 0, st, n, (const uint8_t*)status, (const uint32_t*)sig_aff,
                      sub_bad);
-  hipLaunchKernelGGL(k_sub_reject, dim3(nblk(n, 256)), dim3(256), 0, st, n, (const uint8_t*)sub_bad, status, sig_aff, nbad);
+  hipLaunchKernelGGL(k_sub_reject<fp>, dim3(nblk(n, 256)), dim3(256), 0, st, n, (const uint8_t*)sub_bad, status, sig_aff, nbad);
   return hipGetLastError();
 }
 

@@ -14,7 +14,8 @@ namespace dh {
 // integers in one uint4 (x, y = a; z, w = b): entry e then stands for two points, P_e with scalar a and
 // endo(P_e) (stored half_stride points further on) with scalar b, i.e. P_e with the scalar a + b*mu mod r.
 // G2 (halves = 4): four 31-bit parts (x, y, z, w) for P_e, psi(P_e), psi^2(P_e), psi^3(P_e) (part h at h * half_stride
-// points on), i.e. the scalar a + b z + c z^2 + d z^3 (psi = [z] on G2).
+// points on), i.e. the scalar a + b z + c z^2 + d z^3 (psi = [z] on G2). A G2 batch that takes the batched subgroup
+// test runs with halves = 2: P_e and psi(P_e) with two 63-bit halves, the scalar a + b z.
 struct msm_geom {
   uint32_t gsize;
   int c;
@@ -22,7 +23,7 @@ struct msm_geom {
   uint32_t nbuck;
   uint32_t nseg;
   uint32_t seglen;
-  uint32_t halves;       // 1; 2 for the endomorphism split; 4 for the G2 psi split
+  uint32_t halves;       // 1; 2 for the endomorphism split (G1 phi, G2 psi); 4 for the G2 four-part psi split
   uint32_t half_stride;  // point index offset of endo(P) (halves = 2) / of each psi power (halves = 4)
 };
 inline size_t msm_entries(const msm_geom& g, size_t m) { return m * (size_t)g.nwin * g.halves; }
@@ -40,7 +41,7 @@ struct msm_ws {
   uint32_t* meta;      // balanced bucket pass: 2 words per chunk (head kind, tail key)
   size_t max_entries;  // set by launch_msm_sort: upper bound of sorted-list entries (msm_entries)
   uint32_t* runs = nullptr;  // MSM28: the segments' running sums (as many points as segs)
-  uint32_t* sub = nullptr;   // batched G1 subgroup test (launch_sub_batch): sub_batch_tmp_bytes of scratch
+  uint32_t* sub = nullptr;   // batched subgroup test (launch_sub_batch): sub_batch_tmp_bytes of scratch
 };
 
 // balanced bucket accumulation: entries per chunk, and workspace sizes for `max_entries` list entries
@@ -63,14 +64,14 @@ inline size_t msm_part_bytes(size_t max_entries, size_t jac_words, int nsets) {
 }
 inline size_t msm_meta_bytes(size_t max_entries) { return msm_nchunks(max_entries) * 2 * 4; }
 
-// defer_sub (G1 signatures): decode, curve check, randomness and status only; the subgroup test is left to the batch
-// (launch_sub_batch, or launch_sub_exact when that fails)
+// defer_sub: decode, curve check, randomness and status only (G2: k_dec_sig_g2 without k_sub_sig_g2); the subgroup
+// test is left to the batch (launch_sub_batch, or launch_sub_exact when that fails)
 hipError_t launch_prep(int sig_g2, const uint8_t* sigs, size_t stride, size_t n, uint8_t* status, uint32_t* sig_aff,
                        uint8_t* rand_out, hipStream_t st, bool defer_sub = false);
-// the exact fallback of the batched G1 subgroup test: the per-round test over the n decoded rounds (sub_bad: n bytes of
+// the exact fallback of the batched subgroup test: the per-round test over the n decoded rounds (sub_bad: n bytes of
 // scratch); a failing round gets what the fused launch_prep leaves (status DEC_BAD, the zero point); *nbad (device
 // word) = the number of failing rounds
-hipError_t launch_sub_exact(size_t n, uint8_t* status, uint32_t* sig_aff, uint8_t* sub_bad, uint32_t* nbad, hipStream_t st);
+hipError_t launch_sub_exact(int sig_g2, size_t n, uint8_t* status, uint32_t* sig_aff, uint8_t* sub_bad, uint32_t* nbad, hipStream_t st);
 // small-batch path: the signature pass split at the decoded point (decode + randomness; subgroup test -> sub_bad[i]
 // = 1 when a decoded point is not in the subgroup; verdict[i] = 0 where sub_bad[i])
 hipError_t launch_dec_sig(int sig_g2, const uint8_t* sigs, size_t stride, size_t n, uint8_t* status, uint32_t* sig_aff,
@@ -103,9 +104,10 @@ hipError_t launch_scan(const uint32_t* cnt, size_t nk, uint32_t* off, uint32_t* 
 // The RLC MSM on lazily reduced 28-bit points (k_msm.hip MSM28): launch_msm_prep28 converts the batch's sigma
 // (affine) and hash points (Jacobian, made affine) with their endomorphism images into S and Q (G1 32 / G2 64 words
 // per point, parts x n points each: the images of point i at i + h n; a hash point at infinity marks its round
-// DEC_BAD); the workspace's bucket / partial / segment arrays hold 48 / 96-word Jacobian points
+// DEC_BAD); the workspace's bucket / partial / segment arrays hold 48 / 96-word Jacobian points. parts: 0 = the
+// group's usual split (G1 2, G2 4); 2 for a G2 batch on two psi halves (S and Q then hold 2 n points)
 hipError_t launch_msm_prep28(int sig_g2, size_t n, uint8_t* status, const uint32_t* sig_aff, const uint32_t* q_pts,
-                             uint32_t* S, uint32_t* Q, hipStream_t st, uint32_t sets = 3);
+                             uint32_t* S, uint32_t* Q, hipStream_t st, uint32_t sets = 3, int parts = 0);
 // one point set (S of launch_msm_prep28) with point / scalar / group indices: ngroups 12 x 32-bit Jacobian sums into out
 hipError_t launch_msm28_set(int sig_g2, const msm_geom& g, const uint32_t* pidx, const uint32_t* sidx, const uint32_t* grp,
                             size_t m, size_t ngroups, const uint4* scal, const uint32_t* P, msm_ws& ws, uint32_t* out,
@@ -113,11 +115,11 @@ hipError_t launch_msm28_set(int sig_g2, const msm_geom& g, const uint32_t* pidx,
 hipError_t launch_msm28(int sig_g2, const msm_geom& g, const uint32_t* entries, size_t m, size_t ngroups, const uint4* scal,
                         const uint32_t* S, const uint32_t* Q, msm_ws& ws, uint32_t* outA, uint32_t* outB, hipStream_t st,
                         const uint8_t* skip, bool presorted);
-// The batched G1 subgroup test on the sigma buckets a level-0 launch_msm28 of ONE group left in ws (g: that launch's
-// geometry; ws.sub: sub_batch_tmp_bytes(g)): the bit-subset sums T[w][b] of the buckets, each tested for membership.
+// The batched subgroup test on the sigma buckets a level-0 launch_msm28 of ONE group left in ws (g: that launch's
+// geometry, halves == 2 for either group; ws.sub: sub_batch_tmp_bytes(sig_g2, g)): the bit-subset sums T[w][b] of the buckets, each tested for membership.
 // A failing T clears pass[0] (the level-0 group) and sub_pass[0], which the launch first sets to 1.
-size_t sub_batch_tmp_bytes(const msm_geom& g);
-hipError_t launch_sub_batch(const msm_geom& g, const msm_ws& ws, uint8_t* pass, uint8_t* sub_pass, hipStream_t st);
+size_t sub_batch_tmp_bytes(int sig_g2, const msm_geom& g);
+hipError_t launch_sub_batch(int sig_g2, const msm_geom& g, const msm_ws& ws, uint8_t* pass, uint8_t* sub_pass, hipStream_t st);
 hipError_t launch_msm_sort(const msm_geom& g, const uint32_t* pidx, const uint32_t* sidx, const uint32_t* grp, size_t m,
                            size_t ngroups, const uint4* scal, msm_ws& ws, hipStream_t st);
 hipError_t launch_group_check(int sig_g2, const uint32_t* A, const uint32_t* B, size_t ngroups, const uint32_t* key_aff,

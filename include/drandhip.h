@@ -85,6 +85,9 @@ int dh_key_len(int scheme);
  * high-priority stream): a 4M-round call runs at ~94% of the rate of 8 concurrent 1M calls, a 1M-round call at
  * ~85% (its ~8 ms latency tail, MSM + pairing check, is exposed). DRANDHIP_SPLIT="chunk,workers" / dh_set_split cut a call into
  * chunks verified on several streams instead.
+ * A large batch tests subgroup membership once per batch on the MSM's buckets, with an exact per-round fallback:
+ * DRANDHIP_SUB_BATCH_MIN (G1 signatures, 131072) / DRANDHIP_SUB_BATCH_MIN_G2 (G2 signatures, 393216) rounds and
+ * more; DRANDHIP_SUBGROUP_BATCH=0 keeps the per-round test for both. Verdicts are the same.
  * Returns DH_OK or a negative error code (no verdicts are valid on error).
  */
 int dh_verify_batch(int scheme, const uint8_t* pk, size_t pk_len, const uint64_t* rounds, const uint8_t* sigs,
