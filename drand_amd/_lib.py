@@ -18,6 +18,8 @@ DH_EKEY = -4
 DH_ERECOVER = -5
 DH_EBUSY = -6
 DH_EABANDONED = -7
+DH_ECORRUPT = -8
+DH_ENOBEACON = -9
 DH_NODE_CHECKED = 2
 
 # every symbol declared in include/drandhip.h, with (restype, argtypes)
@@ -59,6 +61,14 @@ SIGNATURES = {
     "dh_batch_stream": (_P, [_P]),
     "dh_check_partials": (_c.c_int, [_c.c_int, _c.c_char_p, _c.c_size_t, _P, _c.c_size_t, _c.POINTER(_c.c_int)]),
     "dh_batch_finish": (_c.c_int, [_P, _c.c_int, _P]),
+    "dh_bolt_index": (_c.c_int, [_P, _c.c_size_t, _P, _P, _c.c_size_t, _P]),
+    "dh_store_open_bolt": (_c.c_int, [_P, _c.c_size_t, _c.POINTER(_P)]),
+    "dh_store_stat": (_c.c_int, [_P, _P]),
+    "dh_store_columns_device": (_c.c_int, [_P, _c.c_uint64, _c.c_uint64, _c.c_size_t, _P, _P, _P, _c.c_size_t, _P, _P,
+                                           _c.c_size_t, _P, _P]),
+    "dh_store_check_past": (_c.c_int, [_P, _c.c_int, _c.c_char_p, _c.c_size_t, _c.c_uint64, _c.c_size_t, _c.c_uint64, _P,
+                                       _c.c_size_t, _P, _P, _P]),
+    "dh_store_close": (None, [_P]),
     "dh_profile": (_c.c_int, [_c.c_int]),
     "dh_profile_read": (_c.c_int, [_c.c_char_p, _c.c_size_t]),
     "dh_last_error_string": (_c.c_char_p, []),

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/drandhip.h"
+#include "bolt.hpp"
 #include "kernels.hpp"
 
 namespace {
@@ -2070,6 +2071,8 @@ int run_split(size_t n, F&& fn, uint64_t seed) {
 
 }  // namespace
 
+static void stores_shutdown();  // store handles, below
+
 extern "C" {
 
 int dh_init(uint32_t device_mask) {
@@ -2078,6 +2081,7 @@ int dh_init(uint32_t device_mask) {
 }
 
 void dh_shutdown(void) {
+  stores_shutdown();  // store handles (dh_store_open_bolt) are invalidated; one inside a call when that call ends
   // idle workers are freed now; a worker leased by a call still running on another thread is retired and freed
   // when that call returns, so the call never touches freed memory
   std::lock_guard<std::mutex> lk(g_ctx.mu);
@@ -2776,6 +2780,379 @@ int dh_public_key(int scheme, const uint8_t* sk32, uint8_t* key_out) {
   HIP_TRY(hipStreamSynchronize(st));
   return DH_OK;
 }
+
+}  // extern "C"
+
+// ---- trimmed bbolt store on the device: chain/boltdb/trimmed.go's read path and the CheckPastBeacons
+// loop over it (chain/beacon/sync_manager.go:170-235). The file image is uploaded once per open store; a window's
+// columns are cut from it by k_bolt.hip in the layout dh_verify_batch_device takes, previous signatures included.
+
+static size_t store_max_bytes() {
+  const char* e = getenv("DRANDHIP_STORE_MAX_BYTES");
+  const long long v = e ? atoll(e) : 0;
+  return v > 0 ? (size_t)v : (size_t)16 << 30;
+}
+
+struct prof_wall {  // host wall time of one store stage (each ends in a stream wait), recorded when profiling is on
+  const char* name;
+  std::chrono::steady_clock::time_point t0;
+  explicit prof_wall(const char* n) : name(n), t0(std::chrono::steady_clock::now()) {}
+  ~prof_wall() {
+    if (g_prof.on.load(std::memory_order_relaxed))
+      g_prof.add(name, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  }
+};
+
+struct dh_store {
+  std::mutex mu;                    // calls on one handle are serialised
+  std::atomic<bool> retire{false};  // dh_shutdown ran while a call held the handle: that call (or the next) releases
+  bool dead = false;                // device memory released by dh_shutdown: every call fails, dh_store_close frees
+  size_t len = 0;
+  uint32_t page_size = 0;
+  uint64_t stat[6] = {0, 0, 0, 0, 0, 0};
+  std::vector<dh::bolt::leaf_info> info;  // the scan's table, one record per leaf in key order
+  std::vector<uint32_t> rleaf;            // the leaves that hold rounds (ascending first / last): the search index
+  hipStream_t st = nullptr;
+  dbuf d_file, d_leaves, d_info, err, cnt, base, scan_tmp, rounds, rows, lens, miss_prev, gap, moff, missing, verdict, bad;
+  std::vector<uint8_t> h_bad;
+  std::vector<uint64_t> h_rounds, h_missing;
+  void release() {
+    for (dbuf* b : {&d_file, &d_leaves, &d_info, &err, &cnt, &base, &scan_tmp, &rounds, &rows, &lens, &miss_prev, &gap, &moff,
+                    &missing, &verdict, &bad})
+      b->release();
+    if (st) (void)hipStreamDestroy(st);
+    st = nullptr;
+    dead = true;
+  }
+};
+static std::mutex g_stores_mu;
+static std::vector<dh_store*> g_stores;
+
+// dh_shutdown: idle handles lose their device memory now, a handle inside a call when that call ends
+static void stores_shutdown() {
+  std::lock_guard<std::mutex> lk(g_stores_mu);
+  for (dh_store* s : g_stores) {
+    if (s->mu.try_lock()) {
+      s->release();
+      s->mu.unlock();
+    } else {
+      s->retire = true;
+    }
+  }
+}
+
+// entered with s->mu held
+static int store_enter(dh_store* s) {
+  if (s->retire.exchange(false)) s->release();
+  if (s->dead) return fail(DH_EINVAL, "store handle invalidated by dh_shutdown (dh_store_close it and open again)");
+  HIP_TRY(hipSetDevice(g_ctx.device));
+  return DH_OK;
+}
+struct store_guard {
+  dh_store* s;
+  explicit store_guard(dh_store* x) : s(x) { s->mu.lock(); }
+  ~store_guard() {
+    if (s->retire.exchange(false)) s->release();
+    s->mu.unlock();
+  }
+};
+
+static int bolt_index(const uint8_t* file, size_t len, dh::bolt::meta* m, std::vector<dh::bolt::leaf_ref>* leaves) {
+  using namespace dh::bolt;
+  const view f{file, (uint64_t)len};
+  uint32_t rc = bolt_meta(f, m);
+  if (!rc) rc = bolt_find_bucket(f, *m, (const uint8_t*)"beacons", 7, leaves);
+  if (rc) return fail(DH_ECORRUPT, "bbolt store: %s", err_name(rc));
+  return DH_OK;
+}
+
+static int store_open(dh_store* s, const uint8_t* file, size_t len) {
+  using namespace dh::bolt;
+  meta m;
+  std::vector<leaf_ref> leaves;
+  {
+    prof_wall p("store_index");
+    int rc = bolt_index(file, len, &m, &leaves);
+    if (rc) return rc;
+  }
+  int rc = ensure_device();
+  if (rc) return rc;
+  const size_t nl = leaves.size();
+  s->len = len;
+  s->page_size = m.page_size;
+  HIP_TRY(hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking));
+  {
+    prof_wall p("store_upload");
+    HIP_TRY(s->d_file.ensure(len));
+    HIP_TRY(hipMemcpyAsync(s->d_file.p, file, len, hipMemcpyHostToDevice, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));
+  }
+  prof_wall p("store_scan");
+  s->info.resize(nl);
+  HIP_TRY(s->d_leaves.ensure(nl * sizeof(leaf_ref)));
+  HIP_TRY(s->d_info.ensure(nl * sizeof(leaf_info)));
+  HIP_TRY(s->err.ensure(4));
+  uint32_t err_word = 0;
+  HIP_TRY(hipMemcpyAsync(s->d_leaves.p, leaves.data(), nl * sizeof(leaf_ref), hipMemcpyHostToDevice, s->st));
+  HIP_TRY(hipMemsetAsync(s->err.p, 0, 4, s->st));
+  HIP_TRY(dh::launch_bolt_scan(s->d_file.as<uint8_t>(), s->d_leaves.p, nl, s->d_info.p, s->err.as<uint32_t>(), s->st));
+  HIP_TRY(hipMemcpyAsync(s->info.data(), s->d_info.p, nl * sizeof(leaf_info), hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipMemcpyAsync(&err_word, s->err.p, 4, hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));
+  uint64_t n_all = 0, n_round = 0, longest = 0;
+  for (size_t i = 0; i < nl; i++) {
+    const leaf_info& li = s->info[i];
+    if (li.err) return fail(DH_ECORRUPT, "bbolt store: leaf %zu at offset %llu: %s", i, (unsigned long long)li.off, err_name(li.err));
+    n_all += li.n_all;
+    n_round += li.n_round;
+    longest = std::max<uint64_t>(longest, li.max_vsize);
+    if (!li.n_round) continue;
+    if (!s->rleaf.empty() && s->info[s->rleaf.back()].last >= li.first)
+      return fail(DH_ECORRUPT, "bbolt store: leaf %zu at offset %llu: %s", i, (unsigned long long)li.off, err_name(E_ORDER));
+    s->rleaf.push_back((uint32_t)i);
+  }
+  if (err_word) return fail(DH_ECORRUPT, "bbolt store: %s", err_name(err_word));
+  s->stat[0] = n_all;
+  s->stat[1] = n_round;
+  s->stat[2] = n_round ? s->info[s->rleaf.front()].first : 0;
+  s->stat[3] = n_round ? s->info[s->rleaf.back()].last : 0;
+  s->stat[4] = longest;
+  s->stat[5] = nl;
+  return DH_OK;
+}
+
+// the window's leaves [lo, lo + nw), its row count (device count + scan; base stays in s->base) and its longest value
+static int store_window(dh_store* s, uint64_t first, uint64_t last, size_t* lo, size_t* nw, size_t* total, uint32_t* longest) {
+  *lo = *nw = *total = 0;
+  *longest = 0;
+  if (first > last) return DH_OK;
+  const auto& rl = s->rleaf;
+  // first leaf whose last round >= first; one past the last leaf whose first round <= last
+  const size_t a = std::partition_point(rl.begin(), rl.end(), [&](uint32_t i) { return s->info[i].last < first; }) - rl.begin();
+  const size_t b = std::partition_point(rl.begin(), rl.end(), [&](uint32_t i) { return s->info[i].first <= last; }) - rl.begin();
+  if (a >= b) return DH_OK;
+  *lo = rl[a];
+  *nw = rl[b - 1] + 1 - rl[a];
+  for (size_t i = *lo; i < *lo + *nw; i++) *longest = std::max(*longest, s->info[i].max_vsize);
+  HIP_TRY(s->cnt.ensure(*nw * 4));
+  HIP_TRY(s->base.ensure((*nw + 1) * 4));
+  HIP_TRY(s->scan_tmp.ensure((*nw / 4096 + 2) * 4));
+  HIP_TRY(dh::launch_bolt_count(s->d_file.as<uint8_t>(), s->d_leaves.as<dh::bolt::leaf_ref>() + *lo,
+                                s->d_info.as<dh::bolt::leaf_info>() + *lo, *nw, first, last, s->cnt.as<uint32_t>(), s->st));
+  HIP_TRY(dh::launch_scan(s->cnt.as<uint32_t>(), *nw, s->base.as<uint32_t>(), s->scan_tmp.as<uint32_t>(), s->st));
+  uint32_t t = 0;
+  HIP_TRY(hipMemcpyAsync(&t, s->base.as<uint32_t>() + *nw, 4, hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));
+  *total = t;
+  return DH_OK;
+}
+
+static size_t window_missing(uint64_t first, uint64_t last, size_t total) {
+  if (first > last) return 0;
+  const uint64_t span = last - first;  // rounds in the window, minus one
+  if (total > span) return 0;  // every round of the window is stored
+  if (span - total == UINT64_MAX) return SIZE_MAX;
+  return (size_t)(span - total + 1);
+}
+
+// after store_window: the rows (total <= cap_rows), miss_prev into s->miss_prev, and the nmiss missing rounds into
+// d_missing when it is given; waits for the stream
+static int store_gather(dh_store* s, size_t lo, size_t nw, size_t total, uint64_t first, uint64_t last, size_t stride,
+                        uint64_t* d_rounds, uint8_t* d_rows, uint32_t* d_lens, size_t cap_rows, uint64_t* d_missing, size_t nmiss) {
+  if (total + 2 > (size_t)4096 * 4096) return fail(DH_EINVAL, "window of %zu rows: at most 16M rows per call", total);
+  timed_launches tl(s->st);  // resolved after the stream wait below
+  if (total)
+    HIP_TRY(tl.run("k_bolt_gather", [&] {
+      return dh::launch_bolt_gather(s->d_file.as<uint8_t>(), s->d_leaves.as<dh::bolt::leaf_ref>() + lo, s->base.as<uint32_t>(), nw, first,
+                                    last, (uint32_t)stride, d_rounds, d_rows, d_lens, cap_rows, s->st);
+    }));
+  HIP_TRY(s->miss_prev.ensure(total + 1));
+  HIP_TRY(s->gap.ensure((total + 1) * 4));
+  HIP_TRY(dh::launch_bolt_link(d_rounds, total, first, last, s->miss_prev.as<uint8_t>(), s->gap.as<uint32_t>(), s->st));
+  if (d_missing && nmiss) {
+    HIP_TRY(s->moff.ensure((total + 2) * 4));
+    HIP_TRY(s->scan_tmp.ensure(((total + 1) / 4096 + 2) * 4));
+    HIP_TRY(dh::launch_scan(s->gap.as<uint32_t>(), total + 1, s->moff.as<uint32_t>(), s->scan_tmp.as<uint32_t>(), s->st));
+    HIP_TRY(dh::launch_bolt_fill(d_rounds, total, first, s->moff.as<uint32_t>(), nmiss, d_missing, s->st));
+  }
+  HIP_TRY(hipStreamSynchronize(s->st));
+  return DH_OK;
+}
+
+extern "C" {
+
+int dh_bolt_index(const uint8_t* file, size_t len, uint32_t* page_size_out, uint64_t* leaf_off_out, size_t cap,
+                  size_t* n_leaves_out) {
+  if (!file || !n_leaves_out) return fail(DH_EINVAL, "null argument");
+  dh::bolt::meta m;
+  std::vector<dh::bolt::leaf_ref> leaves;
+  int rc = bolt_index(file, len, &m, &leaves);
+  if (rc) return rc;
+  if (page_size_out) *page_size_out = m.page_size;
+  *n_leaves_out = leaves.size();
+  if (leaves.size() > cap || (leaves.size() && !leaf_off_out))
+    return fail(DH_EINVAL, "%zu leaves, room for %zu", leaves.size(), cap);
+  for (size_t i = 0; i < leaves.size(); i++) leaf_off_out[i] = leaves[i].off;
+  return DH_OK;
+}
+
+int dh_store_open_bolt(const uint8_t* file, size_t len, dh_store** out) {
+  if (!file || !out) return fail(DH_EINVAL, "null argument");
+  *out = nullptr;
+  if (len > store_max_bytes())
+    return fail(DH_ENOMEM, "store file of %zu bytes exceeds DRANDHIP_STORE_MAX_BYTES (%zu): keep the host reader", len,
+                store_max_bytes());
+  dh_store* s = new dh_store();
+  int rc = store_open(s, file, len);
+  if (rc) {
+    s->release();
+    delete s;
+    return rc;
+  }
+  std::lock_guard<std::mutex> lk(g_stores_mu);
+  g_stores.push_back(s);
+  *out = s;
+  return DH_OK;
+}
+
+int dh_store_stat(const dh_store* s, uint64_t out[6]) {
+  if (!s || !out) return fail(DH_EINVAL, "null argument");
+  memcpy(out, s->stat, sizeof s->stat);  // fixed at open
+  return DH_OK;
+}
+
+void dh_store_close(dh_store* s) {
+  if (!s) return;
+  {
+    std::lock_guard<std::mutex> lk(g_stores_mu);
+    g_stores.erase(std::remove(g_stores.begin(), g_stores.end(), s), g_stores.end());
+  }
+  {
+    std::lock_guard<std::mutex> lk(s->mu);
+    if (!s->dead && hipSetDevice(g_ctx.device) == hipSuccess) s->release();
+  }
+  delete s;
+}
+
+int dh_store_columns_device(dh_store* s, uint64_t first, uint64_t last, size_t row_stride, uint64_t* d_rounds, uint8_t* d_rows,
+                            uint32_t* d_lens, size_t cap_rows, size_t* n_rows_out, uint64_t* d_missing, size_t cap_missing,
+                            size_t* n_missing_out, void* hip_stream) {
+  if (!s || !n_rows_out) return fail(DH_EINVAL, "null argument");
+  if (!row_stride || (row_stride & 3) || row_stride > ((size_t)1 << 20))
+    return fail(DH_EINVAL, "row stride %zu: a positive multiple of 4, at most 1 MiB", row_stride);
+  store_guard g(s);
+  int rc = store_enter(s);
+  if (rc) return rc;
+  prof_wall p("store_gather_link");
+  if (hip_stream) HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));  // the output buffers may be in use there
+  size_t lo, nw, total;
+  uint32_t longest;
+  if ((rc = store_window(s, first, last, &lo, &nw, &total, &longest))) return rc;
+  const size_t nmiss = window_missing(first, last, total);
+  *n_rows_out = total;
+  if (n_missing_out) *n_missing_out = nmiss;
+  if (total > cap_rows || (d_missing && nmiss > cap_missing))
+    return fail(DH_EINVAL, "%zu rows and %zu missing rounds, room for %zu and %zu", total, nmiss, cap_rows, d_missing ? cap_missing : 0);
+  if (total && (!d_rounds || !d_rows || !d_lens)) return fail(DH_EINVAL, "null output");
+  if (d_missing && nmiss > 0xffffffffull) return fail(DH_EINVAL, "%zu missing rounds", nmiss);
+  if (!total && !(d_missing && nmiss)) return DH_OK;
+  return store_gather(s, lo, nw, total, first, last, row_stride, d_rounds, d_rows, d_lens, cap_rows, d_missing, nmiss);
+}
+
+int dh_store_check_past(dh_store* s, int scheme, const uint8_t* pk, size_t pk_len, uint64_t up_to, size_t window, uint64_t seed,
+                        uint64_t* faulty_out, size_t cap, size_t* n_faulty_out,
+                        void (*cb)(uint64_t round, uint64_t up_to, void* arg), void* cb_arg) {
+  if (!s || !pk || !n_faulty_out || (cap && !faulty_out)) return fail(DH_EINVAL, "null argument");
+  if (scheme < 0 || scheme > 3) return fail(DH_EINVAL, "unknown scheme %d", scheme);
+  if (!window) return fail(DH_EINVAL, "window must be >= 1");
+  const uint32_t sig_len = (uint32_t)dh_sig_len(scheme);
+  const bool chained = scheme == DH_SCHEME_CHAINED;
+  store_guard g(s);
+  int rc = store_enter(s);
+  if (rc) return rc;
+  *n_faulty_out = 0;
+  size_t lo, nw, total;
+  uint32_t longest;
+  // store.Last(): the largest round; the chained Get also needs the record before it (trimmed.go:156-193)
+  if (!s->stat[1]) return fail(DH_ENOBEACON, "no beacon stored");
+  const uint64_t last_round = s->stat[3];
+  if (chained && last_round > 0) {
+    if ((rc = store_window(s, last_round - 1, last_round, &lo, &nw, &total, &longest))) return rc;
+    if (total != 2) return fail(DH_ENOBEACON, "no beacon stored: round %llu, before the last", (unsigned long long)(last_round - 1));
+  }
+  if (last_round < up_to) up_to = last_round;
+  const uint64_t store_len = s->stat[0];
+  if (store_len <= 1) return DH_OK;
+  const uint64_t hi = std::min<uint64_t>(store_len - 1, std::max<uint64_t>(up_to, 1));  // the loop's i < len and i >= up_to
+  size_t nf = 0;
+  auto emit = [&](uint64_t r) {
+    if (nf < cap) faulty_out[nf] = r;
+    nf++;
+  };
+  for (uint64_t a = 1; a <= hi;) {
+    const uint64_t b = hi - a < window - 1 ? hi : a + (window - 1);
+    if (cb) cb(a, up_to, cb_arg);
+    const uint64_t g0 = chained ? a - 1 : a;
+    size_t nmiss;
+    size_t stride;
+    {
+      prof_wall p("store_gather_link");
+      if ((rc = store_window(s, g0, b, &lo, &nw, &total, &longest))) return rc;
+      stride = ((size_t)std::max(sig_len, longest) + 3) & ~(size_t)3;
+      if (stride > 65536)
+        return fail(DH_EINVAL, "row stride %zu above 64 KiB (a %u-byte record in rounds %llu..%llu): keep the host reader", stride,
+                    longest, (unsigned long long)g0, (unsigned long long)b);
+      nmiss = window_missing(g0, b, total);
+      HIP_TRY(s->rounds.ensure(total * 8 + 8));
+      HIP_TRY(s->rows.ensure(total * stride + 8));
+      HIP_TRY(s->lens.ensure(total * 4 + 4));
+      HIP_TRY(s->missing.ensure(nmiss * 8 + 8));
+      if ((rc = store_gather(s, lo, nw, total, g0, b, stride, s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
+                             total, s->missing.as<uint64_t>(), nmiss)))
+        return rc;
+    }
+    const size_t off = chained && total ? 1 : 0, nver = total - off;
+    if (nver) {
+      prof_wall p("store_verify");
+      HIP_TRY(s->verdict.ensure(nver));
+      // previous signature of row i = row i - 1 of the same buffer (trimmed.go:183): nothing is copied twice
+      rc = dh_verify_batch_device(scheme, pk, pk_len, s->rounds.as<uint64_t>() + off, s->rows.as<uint8_t>() + off * stride, stride,
+                                  chained ? s->rows.as<uint8_t>() : nullptr, stride, chained ? s->lens.as<uint32_t>() : nullptr, nver,
+                                  s->verdict.as<uint8_t>(), nullptr, seed, nullptr, nullptr);
+      if (rc) return rc;
+    }
+    s->h_bad.resize(total);
+    s->h_rounds.resize(total);
+    s->h_missing.resize(nmiss);
+    if (total) {
+      HIP_TRY(s->bad.ensure(total));
+      HIP_TRY(dh::launch_bolt_fold(s->rounds.as<uint64_t>(), s->lens.as<uint32_t>(), s->miss_prev.as<uint8_t>(), s->verdict.as<uint8_t>(),
+                                   total, sig_len, chained ? 1 : 0, a, s->bad.as<uint8_t>(), s->st));
+      HIP_TRY(hipMemcpyAsync(s->h_bad.data(), s->bad.p, total, hipMemcpyDeviceToHost, s->st));
+      HIP_TRY(hipMemcpyAsync(s->h_rounds.data(), s->rounds.p, total * 8, hipMemcpyDeviceToHost, s->st));
+    }
+    if (nmiss) HIP_TRY(hipMemcpyAsync(s->h_missing.data(), s->missing.p, nmiss * 8, hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));
+    // ascending merge of the missing rounds (the carrier round a - 1 is not examined) and the rows marked bad
+    size_t im = 0;
+    while (im < nmiss && s->h_missing[im] < a) im++;
+    for (size_t i = 0; i < total; i++) {
+      if (!s->h_bad[i]) continue;
+      while (im < nmiss && s->h_missing[im] < s->h_rounds[i]) emit(s->h_missing[im++]);
+      emit(s->h_rounds[i]);
+    }
+    while (im < nmiss) emit(s->h_missing[im++]);
+    if (b == hi) break;
+    a = b + 1;
+  }
+  *n_faulty_out = nf;
+  if (nf > cap) return fail(DH_EINVAL, "%zu faulty rounds, room for %zu", nf, cap);
+  return DH_OK;
+}
+
+}  // extern "C"
+
+extern "C" {
 
 int dh_set_split(uint64_t chunk_rounds, int workers) {
   if (workers < 1) return fail(DH_EINVAL, "workers must be >= 1");

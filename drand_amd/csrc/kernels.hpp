@@ -242,6 +242,24 @@ hipError_t launch_schnorr_check(int key_g2, const uint32_t* sc, const uint8_t* s
 hipError_t launch_schnorr_plain(int key_g2, const uint32_t* sc, const uint8_t* status, const uint32_t* r_aff,
                                 const uint32_t* key_idx, const uint32_t* key_aff, size_t n, uint8_t* verdict, hipStream_t st);
 
+// trimmed bbolt store -> verifier columns (k_bolt.hip). leaves: bolt::leaf_ref records {offset, extent},
+// info: bolt::leaf_info records (40 B), both for the leaves the launch covers (one wave each). count writes the
+// in-range round elements per leaf (then launch_scan: base, n + 1 words); gather writes rounds / lens / value rows of
+// `stride` bytes (a multiple of 4) at base[leaf] + rank; link writes miss_prev (n bytes) and the gaps of [first, last]
+// (n + 1 words; then launch_scan: moff, n + 2 words); fill writes the `total` missing rounds, ascending; fold writes
+// bad[row] (prev_layout: row 0 carries round a - 1, row r was verified as item r - 1).
+hipError_t launch_bolt_scan(const uint8_t* file, const void* leaves, size_t n, void* info, uint32_t* err_word, hipStream_t st);
+hipError_t launch_bolt_count(const uint8_t* file, const void* leaves, const void* info, size_t n, uint64_t first, uint64_t last,
+                             uint32_t* cnt, hipStream_t st);
+hipError_t launch_bolt_gather(const uint8_t* file, const void* leaves, const uint32_t* base, size_t n, uint64_t first, uint64_t last,
+                              uint32_t stride, uint64_t* rounds, uint8_t* rows, uint32_t* lens, uint64_t cap_rows, hipStream_t st);
+hipError_t launch_bolt_link(const uint64_t* rounds, size_t n, uint64_t first, uint64_t last, uint8_t* miss_prev, uint32_t* gap,
+                            hipStream_t st);
+hipError_t launch_bolt_fill(const uint64_t* rounds, size_t n, uint64_t first, const uint32_t* moff, size_t total, uint64_t* missing,
+                            hipStream_t st);
+hipError_t launch_bolt_fold(const uint64_t* rounds, const uint32_t* lens, const uint8_t* miss_prev, const uint8_t* verdict, size_t n,
+                            uint32_t sig_len, int prev_layout, uint64_t a, uint8_t* bad, hipStream_t st);
+
 #ifdef DH_COUNT_PRODUCTS
 // counting build: field products executed since the last take, per translation unit (fp_mul28.hpp)
 hipError_t count_take_prep(unsigned long long* v);

@@ -10,14 +10,19 @@ ingested into the columnar arrays dh_verify_batch takes.
   encoding of chain.Beacon {"PreviousSig","Round","Signature"} (/root/reference/chain/beacon.go:14-39).
 Both expose get / len / last like drand_amd.sync.TrimmedMemStore, so check_past_beacons runs over a real
 store file, plus columns(first, last) for bulk ingestion.
+* DeviceBoltStore — the trimmed layout parsed on the device (libdrandhip dh_store_*): the file image
+  is uploaded once, columns(first, last) come out in device memory in the layout dh_verify_batch_device takes, and
+  check_past_beacons over it is one library call. It agrees with BoltTrimmedStore on every file both accept.
 * hexjson records: client.RandomData {"round","randomness","signature","previous_signature"}
   (/root/reference/client/random.go:5-25) and BeaconPacket-shaped JSON, one object per line or a JSON list.
 """
+import ctypes
 import json
 import struct
 
 import numpy as np
 
+from . import _lib
 from .chain import Beacon
 from .sync import NoBeaconStored
 
@@ -166,6 +171,186 @@ class BoltTrimmedStore(_BoltStoreBase):
             prevs.append(b.previous_signature)
         sig_arr = np.array(sigs, dtype=np.uint8).reshape(-1, sig_len)
         return (np.array(rounds, dtype=np.uint64), sig_arr, prevs if self.requires_previous else None, missing)
+
+
+class StoreTooLarge(MemoryError):
+    """DH_ENOMEM from dh_store_open_bolt: the file exceeds DRANDHIP_STORE_MAX_BYTES or device memory."""
+
+
+class StrideTooLarge(ValueError):
+    """DH_EINVAL from dh_store_check_past: a window's rows would exceed 64 KiB (a huge stored record)."""
+
+
+_CB = ctypes.CFUNCTYPE(None, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p)
+
+
+class DeviceBoltStore:
+    """trimmedStore read path (chain/boltdb/trimmed.go:156-193 of the reference) with the bbolt file parsed on the
+    device: len / last / columns like BoltTrimmedStore, columns_device for tensors that stay in device memory, and
+    check_past (what sync.check_past_beacons calls for this store type): SyncManager.CheckPastBeacons in one
+    dh_store_check_past call. A structurally invalid file raises BoltError from open(), as BoltFile does."""
+
+    def __init__(self, path, requires_previous, open_now=True):
+        self.path = path
+        self.requires_previous = bool(requires_previous)
+        self._h = None
+        self._stat = None
+        if open_now:
+            self.open()
+
+    # ---- handle
+    def open(self):
+        if self._h is not None:
+            return self
+        lib = _lib.load()
+        data = np.fromfile(self.path, dtype=np.uint8)
+        h = ctypes.c_void_p()
+        rc = lib.dh_store_open_bolt(ctypes.c_void_p(data.ctypes.data), data.size, ctypes.byref(h))
+        self._raise(rc)
+        self._h = h
+        st = (ctypes.c_uint64 * 6)()
+        self._raise(lib.dh_store_stat(h, st))
+        self._stat = [int(x) for x in st]
+        return self
+
+    def close(self):
+        if self._h is not None:
+            _lib.load().dh_store_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self.open()
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    @staticmethod
+    def _raise(rc):
+        if rc >= 0:
+            return
+        msg = _lib.last_error()
+        if rc == _lib.DH_ECORRUPT:
+            raise BoltError(msg)
+        if rc == _lib.DH_ENOBEACON:
+            raise NoBeaconStored(msg)
+        if rc == _lib.DH_ENOMEM:
+            raise StoreTooLarge(msg)
+        if rc == _lib.DH_EINVAL:
+            raise ValueError(msg)
+        raise RuntimeError("libdrandhip error %d: %s" % (rc, msg))
+
+    # ---- store interface
+    def len(self):
+        return self._stat[0]
+
+    def rounds_range(self):
+        """(first, last) stored round, or None for a store without round records."""
+        return (self._stat[2], self._stat[3]) if self._stat[1] else None
+
+    def longest_value(self):
+        return self._stat[4]
+
+    def last(self):
+        if not self._stat[1]:
+            raise NoBeaconStored("empty store")
+        return self.get(self._stat[3])
+
+    def get(self, round_):
+        round_ = int(round_)
+        lo = round_ - 1 if self.requires_previous and round_ > 0 else round_
+        rounds, rows, lens, _ = self._columns_host(lo, round_)
+        have = {int(r): rows[i, :lens[i]].tobytes() for i, r in enumerate(rounds)}
+        if round_ not in have:
+            raise NoBeaconStored(round_)
+        prev = b""
+        if lo < round_:
+            if lo not in have:
+                raise NoBeaconStored(lo)
+            prev = have[lo]
+        return Beacon(round_, have[round_], prev)
+
+    def _stride(self, sig_len=0):
+        return max(4, (max(int(sig_len), self._stat[4]) + 3) & ~3)
+
+    def columns_device(self, first, last, stride=None):
+        """Rounds first..last in device memory: (rounds int64[n] (the u64 bit pattern), rows uint8[n, stride],
+        lens int32[n], missing int64[m]) torch tensors; stride defaults to the store's longest value rounded up
+        to 4, so every row holds its record in full."""
+        import torch
+        lib = _lib.load()
+        stride = int(stride or self._stride())
+        first, last = int(first), int(last)
+        n, m = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        rc = lib.dh_store_columns_device(self._h, first, last, stride, None, None, None, 0, ctypes.byref(n), None, 0,
+                                         ctypes.byref(m), None)
+        if rc != _lib.DH_EINVAL or not n.value:  # DH_EINVAL with the sizes needed, unless the window holds no row
+            self._raise(rc)
+        dev = torch.device("cuda")
+        rounds = torch.empty(n.value, dtype=torch.int64, device=dev)
+        rows = torch.empty((n.value, stride), dtype=torch.uint8, device=dev)
+        lens = torch.empty(n.value, dtype=torch.int32, device=dev)
+        missing = torch.empty(m.value, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        self._raise(lib.dh_store_columns_device(self._h, first, last, stride, rounds.data_ptr(), rows.data_ptr(),
+                                                lens.data_ptr(), n.value, ctypes.byref(n), missing.data_ptr(), m.value,
+                                                ctypes.byref(m), None))
+        return rounds, rows, lens, missing
+
+    def _columns_host(self, first, last, sig_len=0):
+        rounds, rows, lens, missing = self.columns_device(first, last, self._stride(sig_len))
+        return (rounds.cpu().numpy().view(np.uint64), rows.cpu().numpy(), lens.cpu().numpy().view(np.uint32),
+                missing.cpu().numpy().view(np.uint64))
+
+    def columns(self, first, last, sig_len):
+        """The tuple of BoltTrimmedStore.columns, from the device columns copied back."""
+        first, last = int(first), int(last)
+        lo = first - 1 if self.requires_previous and first > 0 else first
+        rounds, rows, lens, missing = self._columns_host(lo, last, sig_len)
+        keep = rounds >= first
+        if self.requires_previous:  # Get fails when the record of round - 1 is missing (round 0 has none)
+            has_prev = np.zeros(len(rounds), bool)
+            if len(rounds):
+                has_prev[1:] = rounds[1:] == rounds[:-1] + 1
+                has_prev[0] = rounds[0] == 0
+            lost = rounds[keep & ~has_prev]
+            keep &= has_prev
+        else:
+            lost = np.zeros(0, np.uint64)
+        idx = np.flatnonzero(keep)
+        sig_arr = np.zeros((len(idx), sig_len), np.uint8)
+        good = lens[idx] == sig_len
+        sig_arr[good] = rows[idx[good], :sig_len]
+        prevs = None
+        if self.requires_previous:
+            prevs = [b"" if rounds[i] == 0 else rows[i - 1, :lens[i - 1]].tobytes() for i in idx]
+        miss = sorted(set(int(r) for r in missing if r >= first) | set(int(r) for r in lost))
+        return rounds[idx].astype(np.uint64), sig_arr, prevs, miss
+
+    def check_past(self, scheme, pubkey, up_to, cb=None, window=1 << 20, seed=0):
+        """dh_store_check_past: the faulty rounds of sync.check_past_beacons over this store. cb(round, up_to) is
+        called once per window. Raises StrideTooLarge when the library asks for the host path."""
+        lib = _lib.load()
+        hook = _CB((lambda r, u, _a: cb(int(r), int(u))) if cb is not None else (lambda r, u, _a: None))
+        cap = max(1, self.len())  # the rounds examined lie below len(): one call always has room
+        while True:
+            out = np.zeros(cap, np.uint64)
+            n = ctypes.c_size_t(0)
+            rc = lib.dh_store_check_past(self._h, scheme.id, bytes(pubkey), len(pubkey), int(up_to), int(window), int(seed),
+                                         ctypes.c_void_p(out.ctypes.data), cap, ctypes.byref(n),
+                                         hook if cb is not None else None, None)
+            if rc == _lib.DH_EINVAL and n.value > cap:
+                cap, cb = n.value, None  # the callback has seen every window already
+                continue
+            if rc == _lib.DH_EINVAL and "64 KiB" in _lib.last_error():
+                raise StrideTooLarge(_lib.last_error())
+            self._raise(rc)
+            return [int(x) for x in out[:n.value]]
 
 
 class BoltUntrimmedStore(_BoltStoreBase):

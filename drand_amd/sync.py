@@ -59,7 +59,16 @@ class TrimmedMemStore:
 
 
 def check_past_beacons(store, scheme, pubkey, up_to, cb=None, window=1 << 20, seed=0):
-    """Faulty rounds (ascending) among the stored rounds 1 .. min(up_to, last); [] when all verify."""
+    """Faulty rounds (ascending) among the stored rounds 1 .. min(up_to, last); [] when all verify. A
+    store.DeviceBoltStore takes the whole loop to the device in one dh_store_check_past call (cb then sees the first
+    round of every window, not every round); only when the library refuses the file (too large for the device) or a
+    window (a stored record above 64 KiB) does the loop below run, over a BoltTrimmedStore of the same file."""
+    from . import store as _store
+    if isinstance(store, _store.DeviceBoltStore):
+        try:
+            return store.open().check_past(scheme, pubkey, up_to, cb=cb, window=window, seed=seed)
+        except (_store.StoreTooLarge, _store.StrideTooLarge):
+            store = _store.BoltTrimmedStore(store.path, store.requires_previous)
     last = store.last()
     if last.round < up_to:
         up_to = last.round

@@ -20,7 +20,9 @@
  *   sign.Scheme.Verify (DKGAuthScheme)    [kyber v1.1.18 sign/schnorr], crypto/schemes.go:103,144,184, called at
  *                                         core/drand_beacon_control.go:354,476 and core/group_setup.go:384
  * and adds the batch entry point the serial per-round loops need:
- *   chain/beacon/sync_manager.go:191-225 (CheckPastBeacons), client/verify.go:139-160, lp2p relays.
+ *   chain/beacon/sync_manager.go:191-225 (CheckPastBeacons), client/verify.go:139-160, lp2p relays;
+ * and the read path of the trimmed bolt store that loop runs over, parsed on the device from the store file:
+ *   chain/boltdb/trimmed.go:87-107,156-193 (dh_store_*).
  * INTEGRATION.md shows the cgo binding a drand maintainer would add.
  */
 #ifndef DRANDHIP_H
@@ -43,6 +45,8 @@ extern "C" {
 #define DH_EBUSY (-6)    /* every library worker is held (DRANDHIP_MAX_WORKERS, default 24): dh_batch_begin at once,
                             a blocking call after DRANDHIP_LEASE_TIMEOUT_MS when node batches hold them all */
 #define DH_EABANDONED (-7) /* node-wide batch: some rank's dh_batch_begin failed, every rank abandons the batch */
+#define DH_ECORRUPT (-8)   /* the store file is structurally invalid (which check failed: dh_last_error_string) */
+#define DH_ENOBEACON (-9)  /* chainerrors.ErrNoBeaconStored: empty store, or Last() has no previous record (chained) */
 
 /* scheme ids, in the order of crypto/schemes.go:206-219 plus the RFC 9380 quicknet scheme */
 #define DH_SCHEME_CHAINED 0      /* "pedersen-bls-chained":   sig G2 (96 B), key G1 (48 B), msg SHA256(prev||round) */
@@ -268,6 +272,67 @@ void* dh_batch_stream(dh_batch* batch);
 int dh_batch_check(dh_batch* batch, const uint8_t* d_partials, size_t k, void* hip_stream);
 int dh_check_partials(int scheme, const uint8_t* pk, size_t pk_len, const uint8_t* d_partials, size_t k, int* pass_out);
 int dh_batch_finish(dh_batch* batch, int node_pass, uint64_t stats_out[4]);
+
+/*
+ * Trimmed bbolt chain stores on the device: the read path of chain/boltdb/trimmed.go:87-107,156-193 (bucket "beacons",
+ * key = round as 8 bytes big-endian, value = the raw signature, PreviousSig of round r = the stored value of r - 1;
+ * the default layout of every new store, chain/boltdb/store.go:82-93) and the CheckPastBeacons loop over it
+ * (chain/beacon/sync_manager.go:170-235), without the serial bbolt cursor. `file` is the image of the store file
+ * (go.etcd.io/bbolt format v2, any page size: the meta page names it), e.g. a read-only mmap; it is borrowed for the
+ * call. Every structural defect of the file is DH_ECORRUPT, never a read outside [file, file + len).
+ *
+ * dh_bolt_index: host only, no device (like dh_identity_hash_batch). What a bbolt cursor does before its first Next():
+ * the valid meta page with the larger txid, the "beacons" entry of the root bucket, then the branch pages depth-first
+ * in key order: one BYTE OFFSET per leaf (an inline bucket is the one leaf inside its bucket value). More than `cap`
+ * leaves: DH_EINVAL with *n_leaves_out = the number needed.
+ */
+int dh_bolt_index(const uint8_t* file, size_t len, uint32_t* page_size_out, uint64_t* leaf_off_out, size_t cap,
+                  size_t* n_leaves_out);
+
+/*
+ * Open a store: index the file on the host, upload the image (it stays resident in device memory until close: a
+ * mainnet-size store is ~0.6 GB), validate and summarise every leaf on the device. Files above
+ * DRANDHIP_STORE_MAX_BYTES (default 16 GiB) are refused with DH_ENOMEM, as is a failed allocation: the caller keeps
+ * its host reader. Replaces boltdb.newTrimmedStore's bolt.Open for reading (chain/boltdb/trimmed.go:47-85).
+ * Handles are independent of the library's workers; calls on one handle from several threads are serialised by a
+ * mutex in the handle. dh_shutdown invalidates every handle (a handle inside a call when that call returns): later
+ * calls on it fail with DH_EINVAL and only dh_store_close is valid.
+ */
+typedef struct dh_store dh_store;
+int dh_store_open_bolt(const uint8_t* file, size_t len, dh_store** out);
+/* Store.Len / the cursor's First and Last (trimmed.go:109-122,195-221): out = {len (every element of the bucket that
+ * is not a nested bucket, as Len counts keys), round records (8-byte keys), first round, last round, longest value
+ * in bytes, leaves} */
+int dh_store_stat(const dh_store* store, uint64_t out[6]);
+/*
+ * The records of rounds first..last as columns in device memory, in key order (the cursor walk of
+ * trimmedStore.Cursor / Get, trimmed.go:156-193,223-262, for a whole range): d_rounds[i], d_lens[i] = the stored length,
+ * the value at d_rows + i*row_stride (row_stride a multiple of 4, at most 1 MiB), copied in full and zero-padded when it fits and left
+ * ALL ZERO when it is longer than row_stride (never cut to a prefix: a wrong-length record must not decode). d_missing
+ * (nullable) receives the rounds of [first, last] with no record, ascending. The layout serves the verifier with no
+ * second copy: gather first-1..last and pass d_sigs = d_rows + row_stride, d_prevs = d_rows, d_prev_lens = d_lens,
+ * d_rounds + 1 to dh_verify_batch_device. Too little room (cap_rows, cap_missing): DH_EINVAL with *n_rows_out and
+ * *n_missing_out = the sizes needed and nothing written; at most 16M rows per call. Outputs still in use on
+ * hip_stream (nullable) are waited for; the call blocks until the columns are complete.
+ */
+int dh_store_columns_device(dh_store* store, uint64_t first, uint64_t last, size_t row_stride, uint64_t* d_rounds,
+                            uint8_t* d_rows, uint32_t* d_lens, size_t cap_rows, size_t* n_rows_out, uint64_t* d_missing,
+                            size_t cap_missing, size_t* n_missing_out, void* hip_stream);
+/*
+ * SyncManager.CheckPastBeacons (chain/beacon/sync_manager.go:170-235) over the store: the faulty rounds, ascending,
+ * among rounds 1 .. min(up_to, Last().Round), visited while round < Len() as that loop does. A round is faulty when
+ * its record is missing, when the scheme is chained and the record of round - 1 is missing (the Get error of
+ * trimmed.go:183-190), when its stored length is not dh_sig_len, or when dh_verify_batch_device rejects it. Rounds are
+ * verified `window` at a time on the columns in place, rows of roundup4(max(dh_sig_len, the longest value in the
+ * window's leaves)) bytes, so an odd-length stored record is hashed as stored and marks only its own round; a window
+ * whose rows would exceed 64 KiB is DH_EINVAL (keep the host path). `cb` (nullable) is called ONCE PER WINDOW with the
+ * window's first round, not once per round as the reference's callback is. More than `cap` faulty rounds: every round
+ * is still counted, DH_EINVAL with *n_faulty_out = the number needed. DH_ENOBEACON when Last() fails.
+ */
+int dh_store_check_past(dh_store* store, int scheme, const uint8_t* pk, size_t pk_len, uint64_t up_to, size_t window,
+                        uint64_t seed, uint64_t* faulty_out, size_t cap, size_t* n_faulty_out,
+                        void (*cb)(uint64_t round, uint64_t up_to, void* arg), void* cb_arg);
+void dh_store_close(dh_store* store);
 
 /*
  * Synthetic-chain utilities (test fixtures and benchmark inputs; not part of the verification path):
