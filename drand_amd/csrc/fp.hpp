@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "consts.hpp"
 #include "fp_mul28.hpp"
+#include "fp_mul30.hpp"
 #include "inv_bingcd.hpp"
 
 namespace dh {
@@ -329,14 +330,14 @@ DH_DEV fp fp_mul_c(const fp& a, const uint32_t* c) { return fp_mul(a, fp_c(c)); 
 // table x, x^3, ..., x^15 and the all-ones entry x^255 (the exponents have runs of 33, 19 and 17 ones); sched[0] =
 // first table index, then (squarings << 8 | index), index 0xff = squarings only. ~380 squarings + 76 products for
 // the 381-bit exponents (w = 3 in registers: 378 + 109; binary: ~228 products).
-// The table (SCHED_TAB x 56 bytes) does not fit in registers beside a product's working set at two waves per SIMD,
+// The table (SCHED_TAB x 52 bytes) does not fit in registers beside a product's working set at two waves per SIMD,
 // so it lives in per-lane scratch: every lane of a wave reads the same entry (the index comes from the wave-uniform
 // schedule), the load of a step's entry is issued BEFORE the step's squarings, which hide its latency, and the
-// entry occupies 14 VGPRs only from there to its product.
-// The chain runs on 14 x 28-bit limbs in Montgomery radix R' = 2^392 (fp_mul28.hpp mont_mul / mont_sqr, inlined):
-// x R enters as x R' by one product with 2^400 mod p and leaves by one product with 2^384 mod p, so the ~460
-// products in between skip the 12 <-> 14 limb slicing and the final subtraction of the out-of-line bodies
-// (~110 of their ~610 instructions). Every intermediate value stays < 1.002 p with normalised limbs.
+// entry occupies 13 VGPRs only from there to its product.
+// Until r11 the chain ran on 14 x 28-bit limbs in Montgomery radix R' = 2^392 (fp_mul28.hpp mont_mul / mont_sqr, inlined):
+// x R entered as x R' by one product with 2^400 mod p and left by one product with 2^384 mod p, so the ~460
+// products in between skipped the 12 <-> 14 limb slicing and the final subtraction of the out-of-line bodies
+// (~110 of their ~610 instructions), every intermediate value < 1.002 p with normalised limbs.
 struct fp28 {
   uint32_t l[14];
 };
@@ -374,45 +375,25 @@ DH_DEV fp fp28_to(const fp28& a) {  // x R' -> x R, canonical
   return o;
 }
 
-// the chain on a value already in the 28-bit form (x R', < 2p, normalised limbs), result in the same form
-DH_DEV fp28 fp28_pow_sched(const fp28& x, const uint32_t* sched, int len) {
-  fp28 tab[cst::SCHED_TAB];
-  {
-    const fp28 x2 = fp28_sqr(x);
-    fp28 t = x;
-    tab[0] = t;
-#pragma unroll 1
-    for (int k = 1; k < cst::SCHED_ODD; k++) {
-      t = fp28_mul(t, x2);
-      tab[k] = t;
-    }
-    // t = x^(2^r - 1), r = SCHED_W: each run entry doubles r
-#pragma unroll 1
-    for (int k = 0, r = cst::SCHED_W; k < cst::SCHED_RUNS; k++, r *= 2) {
-      const fp28 h = t;
-#pragma unroll 1
-      for (int j = 0; j < r; j++) t = fp28_sqr(t);
-      t = fp28_mul(t, h);
-      tab[cst::SCHED_ODD + k] = t;
-    }
-  }
-  fp28 acc = tab[sched[0]];
-  uint32_t next = sched[1];  // the tables end with a 0 entry: the read one step ahead stays in bounds
-#pragma unroll 1
-  for (int i = 1; i < len; i++) {
-    const uint32_t op = next;
-    next = sched[i + 1];  // scalar load issued a whole step before its use
-    const uint32_t nsq = op >> 8, k = op & 0xff;
-    const fp28 e = tab[k == 0xff ? 0 : k];  // issued before the squarings
-#pragma unroll 1
-    for (uint32_t j = 0; j < nsq; j++) acc = fp28_sqr(acc);
-    if (k != 0xff) acc = fp28_mul(acc, e);
-  }
-  return acc;
+// The chains themselves run on 13 signed 30-bit digits in Montgomery radix 2^390 (fp_mul30.hpp: 338 MADs a product and
+// 260 a squaring against 392 and 301 here, values 13 registers wide, table entries 52 bytes): fp30_from / fp30_to are
+// the entry (slices recentred, one product with 2^396 mod p) and the exit (one product with 2^384 mod p, + p where
+// negative, canonical words), fp30_pow_sched the table build and the loop described above, unchanged in structure. The
+// 28-bit fp28_mul / fp28_sqr / fp28_from / fp28_to above stay for their other users (bench/microbench_fp30.hip).
+typedef m30::el fp30;
+DH_DEV fp30 fp30_from(const fp& x) { return m30::from(x.v); }  // x R -> x 2^390
+DH_DEV fp fp30_to(const fp30& a) {                             // x 2^390 -> x R, canonical
+  fp o;
+  m30::to(o.v, a);
+  return o;
+}
+// the chain on a value already in the 30-bit form (|x| < 0.51 p, centred digits), result in the same form
+DH_DEV fp30 fp30_pow_sched(const fp30& x, const uint32_t* sched, int len) {
+  return m30::pow_sched<cst::SCHED_W, cst::SCHED_ODD, cst::SCHED_RUNS>(x, sched, len);
 }
 
 DH_DEV fp fp_pow_sched(const fp& x0, const uint32_t* sched, int len) {
-  return fp28_to(fp28_pow_sched(fp28_from(x0), sched, len));
+  return fp30_to(fp30_pow_sched(fp30_from(x0), sched, len));
 }
 
 DH_DEV fp fp_inv(const fp& x) { return fp_pow_sched(x, cst::SCHED_INV, cst::SCHED_INV_LEN); }

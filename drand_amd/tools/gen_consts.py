@@ -249,7 +249,7 @@ def window_schedule(e, wbits):
     return ops
 
 
-# The Fp chains' dictionary (fp.hpp fp28_pow_sched): the odd powers x^1 .. x^(2^SCHED_W - 1) (indices 0 ..
+# The Fp chains' dictionary (fp.hpp fp30_pow_sched, fp_mul30.hpp pow_sched): the odd powers x^1 .. x^(2^SCHED_W - 1) (indices 0 ..
 # SCHED_ODD - 1) and SCHED_RUNS all-ones entries x^(2^r - 1), r = 2 SCHED_W, 4 SCHED_W, ... (each built from the
 # entry before it, which is x^(2^(r/2) - 1), by r/2 squarings and one product). The exponents have runs of 33, 19 and
 # 17 ones. Counted for (p + 1) / 4, the others within 0.4% (optimal parse, 392 MADs per product, 301 per squaring,
@@ -434,7 +434,7 @@ def main():
         w("constexpr int %s_BITS = %d;" % (name, e.bit_length()))
         w("__device__ __constant__ uint32_t %s[%d] = %s;" % (name, n, txt))
     # schedules for the fixed exponents: entry = (squarings << 8) | table index, index 0xff = squarings only (trailing
-    # zeros). Fp: the dictionary above (fp.hpp fp28_pow_sched); Fp2 (SCHED_SR2_C3, fp2.hpp fp2_pow_sched): sliding
+    # zeros). Fp: the dictionary above (fp.hpp fp30_pow_sched, fp_mul30.hpp pow_sched); Fp2 (SCHED_SR2_C3, fp2.hpp fp2_pow_sched): sliding
     # window, w = 3, odd powers x^1,3,5,7
     w("constexpr int SCHED_W = %d;     // Fp chains: odd powers below 2^SCHED_W ..." % SCHED_W)
     w("constexpr int SCHED_ODD = %d;   // ... at indices 0 .. SCHED_ODD - 1," % (1 << (SCHED_W - 1)))
