@@ -42,6 +42,8 @@ def main():
     # the bucket sums is counted per round of its batch
     if "k_sub_batch_level0" in q:
         units["k_sub_batch_level0"] = q["k_sub_batch_level0"]
+    if "k_sub_batch_level0" in u:  # the batched G2 subgroup test, at batches of its minimum size and above
+        units["k_sub_batch_level0<fp2>"] = u["k_sub_batch_level0"]
     if rec_r is not None:  # random signer subsets: every round its own basis, the regular-window chains
         units["k_lagrange_t33_random"] = rec_r["k_lagrange"]
         units["k_wnaf_table_t33_random"] = rec_r.get("k_wnaf_table", 0.0)
@@ -50,7 +52,8 @@ def main():
     wm["executed_M_per_beacon"] = {
         "g1_sig": round(units["k_prep_sig<fp>"] + units["k_prep_msg<fp>"] + units["msm_level0"]
                         + units.get("k_sub_batch_level0", 0.0), 1),
-        "g2_sig": round(units["k_prep_sig<fp2>"] + units["k_prep_msg<fp2>"] + units["msm_level0<fp2>"], 1),
+        "g2_sig": round(units["k_prep_sig<fp2>"] + units["k_prep_msg<fp2>"] + units["msm_level0<fp2>"]
+                        + units.get("k_sub_batch_level0<fp2>", 0.0), 1),
     }
     wm["counts_source"] = os.path.relpath(src, os.path.dirname(HERE))
     wm["_doc_credit"] = ("kernel_units_M_per_round and executed_M_per_beacon are COUNTED executed field products per "
@@ -63,7 +66,11 @@ def main():
                          "DRANDHIP_SUB_BATCH_MIN still run the fused kernel (1532.0 M per round counted in r07, 1501.0 with the "
                          "r08 square-root chain, which the decode-only kernel was counted to save: g1_sig 2831.4). r08: "
                          "the fixed-exponent Fp chains run on a nine-entry dictionary (DESIGN 13): 78 products and 380 "
-                         "squarings per chain instead of 110-111 and 378")
+                         "squarings per chain instead of 110-111 and 378. r12: the hash isogenies run on their kernel polynomials "
+                         "(DESIGN 17): k_prep_msg<fp> 1123 -> 1074, k_prep_msg<fp2> 2155 -> 2099; the G2 figures are now "
+                         "those of a 1,048,576-round batch with the batched G2 subgroup test of r09 (DESIGN 14: "
+                         "k_prep_sig<fp2> = the decode-only kernel, 935 where the fused kernel counts 2138, plus "
+                         "k_sub_batch_level0<fp2>), which r09 had not carried into this file")
     wm.pop("_doc_k_lagrange", None)
     with open(wm_path, "w") as f:
         json.dump(wm, f, indent=2)

@@ -72,39 +72,44 @@ DH_DEV swu_out<fp> sswu_g1(const fp& u) {
   return {x, tv4, y};
 }
 
-// 11-isogeny E1' -> E1 (RFC 9380 E.2) on a Jacobian point of E1' (x = X/Z^2, y = Y/Z^3), Jacobian output,
-// Z' = 0 if a denominator vanishes (the point is in the isogeny's kernel: its image is the identity).
-// Homogeneous Horner in x = X / D with D = Z^2: acc_d = acc_d * X + c_{d-j} * D^j, j = 1..deg.
-// Evaluated on lazily reduced 28-bit limbs (fp28.hpp): the ~120 products skip the 12 <-> 14 limb slicing and the
-// Horner sums skip their reductions (every accumulator stays < 4p, a product input up to ~50p); three conversion
-// products in (X, Y, Z) and three out.
+// 11-isogeny E1' -> E1 (RFC 9380 E.2) on a Jacobian point of E1' (x = X/Z^2, y = Y/Z^3), Jacobian output.
+// The map is a normalised isogeny with kernel polynomial h (monic, degree 5): x_den = h^2 and y_den = h^3
+// (gen_consts.py kernel_poly derives h and checks both), so only x_num, y_num and h are evaluated. Homogeneous Horner
+// in x = X / D with D = Z^2 over one sequence of D powers, acc = acc * X + c_{d-j} * D^j for j = 1..d, gives
+//   xn_h = D^11 x_num(x), yn_h = D^15 y_num(x), h_h = D^5 h(x), and then
+//   x' = x_num / h^2 = xn_h / (D h_h^2),  y' = (Y / Z^3) y_num / h^3 = Y yn_h / (Z^3 h_h^3):
+// with Z' = Z h_h (Z'^2 = D h_h^2, Z'^3 = Z^3 h_h^3) the Jacobian image is (X', Y', Z') = (xn_h, Y yn_h, Z h_h).
+// Z' = 0 exactly when Z = 0 (the identity; then D = 0 and h_h = X^5) or h(x) = 0 (the point is in the isogeny's
+// kernel: its image is the identity): Fp has no zero divisors and Z' is returned canonical. X' and Y' are then
+// arbitrary, as jac_is_inf looks at Z alone.
+// Evaluated on lazily reduced 28-bit limbs (fp28.hpp): the products skip the 12 <-> 14 limb slicing and the Horner
+// sums skip their reductions. Value bounds in units of p: a product's result is < 2, a Horner accumulator (the sum
+// of two) < 4, X < 2, so every product here is at most 4 x 2; X' = xn_h < 4 goes to f28_to_fp, whose product by a
+// constant < 1 accepts it. h is monic, so its first step is X + c_4 D with one product instead of two. 78 products:
+// 15 + 11 + 5 Horner steps of two each less that one (61), 14 D powers, D, Y yn_h and Z h_h (127 with the four printed
+// polynomials); three conversion products in (X, Y, Z) and three out, as before.
 DH_DEV jac<fp> iso11_jac(const jac<fp>& p) {
   using namespace cst;
-  const f28 X = f28_from_fp(p.x), Zp = f28_from_fp(p.z);
+  const f28 X = f28_from_fp(p.x), Zp = f28_from_fp(p.z);              // < 2
   const f28 D = f28_sqr(Zp);                                            // < 2
-  f28 xn = f28_c(ISO11_XNUM_28[ISO11_XNUM_LEN - 1]);
-  f28 xd = f28_c(ISO11_XDEN_28[ISO11_XDEN_LEN - 1]);
-  f28 yn = f28_c(ISO11_YNUM_28[ISO11_YNUM_LEN - 1]);
-  f28 yd = f28_c(ISO11_YDEN_28[ISO11_YDEN_LEN - 1]);
+  f28 xn = f28_c(ISO11_XNUM_28[ISO11_XNUM_LEN - 1]);                    // < 1
+  f28 yn = f28_c(ISO11_YNUM_28[ISO11_YNUM_LEN - 1]);                    // < 1
+  f28 h = X;                                                            // the leading coefficient is 1
   f28 zp = D;
 #pragma unroll 1
   for (int j = 1; j < ISO11_YNUM_LEN; j++) {
     if (j > 1) zp = f28_mul(zp, D);                                     // < 2
     yn = f28_add(f28_mul(yn, X), f28_mul(f28_c(ISO11_YNUM_28[ISO11_YNUM_LEN - 1 - j]), zp));  // < 4
-    yd = f28_add(f28_mul(yd, X), f28_mul(f28_c(ISO11_YDEN_28[ISO11_YDEN_LEN - 1 - j]), zp));
     if (j < ISO11_XNUM_LEN) xn = f28_add(f28_mul(xn, X), f28_mul(f28_c(ISO11_XNUM_28[ISO11_XNUM_LEN - 1 - j]), zp));
-    if (j < ISO11_XDEN_LEN) xd = f28_add(f28_mul(xd, X), f28_mul(f28_c(ISO11_XDEN_28[ISO11_XDEN_LEN - 1 - j]), zp));
+    if (j < ISO11_H_LEN) {
+      const f28 t = f28_mul(f28_c(ISO11_H_28[ISO11_H_LEN - 1 - j]), zp);
+      h = f28_add(j > 1 ? f28_mul(h, X) : h, t);                        // < 4
+    }
   }
-  // x' = xn / (xd D) = Nx / a, y' = (Y / Z^3) yn / yd = Ny / (Z^3 yd)   (deg xn = deg xd + 1, deg yn = deg yd)
-  // Z' = a yd Z^3, X' = Nx yd Z^3 Z', Y' = Y yn a Z'^2
-  const f28 a = f28_mul(xd, D);
-  const f28 z3 = f28_mul(D, Zp);
-  const f28 ydz3 = f28_mul(yd, z3);
-  const f28 rz = f28_mul(a, ydz3);
   jac<fp> r;
-  r.z = f28_to_fp(rz);
-  r.x = f28_to_fp(f28_mul(f28_mul(xn, ydz3), rz));
-  r.y = f28_to_fp(f28_mul(f28_mul(f28_mul(f28_from_fp(p.y), yn), a), f28_sqr(rz)));
+  r.x = f28_to_fp(xn);
+  r.y = f28_to_fp(f28_mul(f28_from_fp(p.y), yn));
+  r.z = f28_to_fp(f28_mul(Zp, h));
   return r;
 }
 
@@ -187,72 +192,33 @@ DH_DEV swu_out<fp2> sswu_g2(const fp2& u) {
   return {x, tv4, y};
 }
 
-// 3-isogeny E2' -> E2 (RFC 9380 E.3) on a Jacobian point of E2', same homogeneous evaluation as iso11_jac
+// 3-isogeny E2' -> E2 (RFC 9380 E.3) on a Jacobian point of E2', in the kernel-polynomial form of iso11_jac: here
+// h = x + ISO3_H[0] (x_den = h^2, y_den = h^3, checked by gen_consts.py kernel_poly) and x_num, y_num both have
+// degree 3, so with D = Z^2, xn_h = D^3 x_num(X / D), yn_h = D^3 y_num(X / D), h_h = X + ISO3_H[0] D:
+//   x' = xn_h / (D h_h^2), y' = Y yn_h / (Z^3 h_h^3), (X', Y', Z') = (xn_h, Y yn_h, Z h_h).
+// Z' = 0 exactly when Z = 0 or h(x) = 0 (the point is in the kernel: its image is the identity).
+// 18 Fp2 products (35 with the four printed polynomials); seven Fp2 values are live in the loop (p, D, D^j, xn, yn),
+// which is what the G2 pass kernels (k_prep.hip) can hold, so they use it as it is.
 DH_DEV jac<fp2> iso3_jac(const jac<fp2>& p) {
   using namespace cst;
+  static_assert(ISO3_XNUM_LEN == ISO3_YNUM_LEN && ISO3_H_LEN == 2, "iso3_jac: degrees 3, 3 and 1");
   const fp2 D = fp2_sqr(p.z);
   fp2 xn = fp2_c(ISO3_XNUM[ISO3_XNUM_LEN - 1]);
-  fp2 xd = fp2_c(ISO3_XDEN[ISO3_XDEN_LEN - 1]);
   fp2 yn = fp2_c(ISO3_YNUM[ISO3_YNUM_LEN - 1]);
-  fp2 yd = fp2_c(ISO3_YDEN[ISO3_YDEN_LEN - 1]);
   fp2 zp = D;
 #pragma unroll 1
   for (int j = 1; j < ISO3_YNUM_LEN; j++) {
     if (j > 1) zp = fp2_mul(zp, D);
     yn = fp2_add(fp2_mul(yn, p.x), fp2_mul(fp2_c(ISO3_YNUM[ISO3_YNUM_LEN - 1 - j]), zp));
-    yd = fp2_add(fp2_mul(yd, p.x), fp2_mul(fp2_c(ISO3_YDEN[ISO3_YDEN_LEN - 1 - j]), zp));
-    if (j < ISO3_XNUM_LEN) xn = fp2_add(fp2_mul(xn, p.x), fp2_mul(fp2_c(ISO3_XNUM[ISO3_XNUM_LEN - 1 - j]), zp));
-    if (j < ISO3_XDEN_LEN) xd = fp2_add(fp2_mul(xd, p.x), fp2_mul(fp2_c(ISO3_XDEN[ISO3_XDEN_LEN - 1 - j]), zp));
-  }
-  const fp2 a = fp2_mul(xd, D);
-  const fp2 z3 = fp2_mul(D, p.z);
-  const fp2 ydz3 = fp2_mul(yd, z3);
-  jac<fp2> r;
-  r.z = fp2_mul(a, ydz3);
-  r.x = fp2_mul(fp2_mul(xn, ydz3), r.z);
-  r.y = fp2_mul(fp2_mul(fp2_mul(p.y, yn), a), fp2_sqr(r.z));
-  return r;
-}
-
-// Register-lean forms for the G2 pass kernels (k_prep.hip): the same maps as iso3_jac / jac_add_distinct with
-// the operations reordered so that at most ~7 Fp2 values are live at once (one lane holds ~10 in 256 VGPRs).
-// Same points; the Jacobian representatives differ (Z scaled), which no consumer depends on.
-//
-// iso3 with the y-part first: Ny = Y yn and yd Z^3 collapse before the x-part's Horner runs.
-DH_DEV jac<fp2> iso3_jac_lean(const jac<fp2>& p) {
-  using namespace cst;
-  const fp2 D = fp2_sqr(p.z);
-  fp2 ydz3;
-  fp2 ny;
-  {
-    fp2 yn = fp2_c(ISO3_YNUM[ISO3_YNUM_LEN - 1]);
-    fp2 yd = fp2_c(ISO3_YDEN[ISO3_YDEN_LEN - 1]);
-    fp2 zp = D;
-#pragma unroll 1
-    for (int j = 1; j < ISO3_YNUM_LEN; j++) {
-      if (j > 1) zp = fp2_mul(zp, D);
-      yn = fp2_add(fp2_mul(yn, p.x), fp2_mul(fp2_c(ISO3_YNUM[ISO3_YNUM_LEN - 1 - j]), zp));
-      yd = fp2_add(fp2_mul(yd, p.x), fp2_mul(fp2_c(ISO3_YDEN[ISO3_YDEN_LEN - 1 - j]), zp));
-    }
-    ydz3 = fp2_mul(yd, fp2_mul(D, p.z));
-    ny = fp2_mul(p.y, yn);
-  }
-  fp2 xn = fp2_c(ISO3_XNUM[ISO3_XNUM_LEN - 1]);
-  fp2 xd = fp2_c(ISO3_XDEN[ISO3_XDEN_LEN - 1]);
-  fp2 zp = D;
-#pragma unroll 1
-  for (int j = 1; j < ISO3_XNUM_LEN; j++) {
-    if (j > 1) zp = fp2_mul(zp, D);
     xn = fp2_add(fp2_mul(xn, p.x), fp2_mul(fp2_c(ISO3_XNUM[ISO3_XNUM_LEN - 1 - j]), zp));
-    if (j < ISO3_XDEN_LEN) xd = fp2_add(fp2_mul(xd, p.x), fp2_mul(fp2_c(ISO3_XDEN[ISO3_XDEN_LEN - 1 - j]), zp));
   }
-  const fp2 a = fp2_mul(xd, D);
   jac<fp2> r;
-  r.z = fp2_mul(a, ydz3);
-  r.x = fp2_mul(fp2_mul(xn, ydz3), r.z);
-  r.y = fp2_mul(fp2_mul(ny, a), fp2_sqr(r.z));
+  r.x = xn;
+  r.y = fp2_mul(p.y, yn);
+  r.z = fp2_mul(p.z, fp2_add(p.x, fp2_mul(fp2_c(ISO3_H[0]), D)));
   return r;
 }
+DH_DEV jac<fp2> iso3_jac_lean(const jac<fp2>& p) { return iso3_jac(p); }
 
 // hash_to_curve(G2) without clear_cofactor, one isogeny after the addition on E2' (see h2c_g1_noclear)
 DH_DEV jac<fp2> h2c_g2_map(const fp2& u0, const fp2& u1) {

@@ -136,6 +136,39 @@ def f2inv(a):
     return (a[0] * n % P, (-a[1]) * n % P)
 
 
+def poly_mul(a, b):
+    """Product of two polynomials over Fp2 (coefficient lists, low degree first)."""
+    r = [(0, 0)] * (len(a) + len(b) - 1)
+    for i, x in enumerate(a):
+        for j, y in enumerate(b):
+            t = f2mul(x, y)
+            r[i + j] = ((r[i + j][0] + t[0]) % P, (r[i + j][1] + t[1]) % P)
+    return r
+
+
+def kernel_poly(xden, yden):
+    """The isogeny's kernel polynomial h: the monic square root of x_den, from the top coefficient down (the
+    coefficient of x^(2d-k) in h^2 is 2 h_(d-k) plus products of coefficients already known). RFC 9380 prints the four
+    polynomials of each map independently; the maps are normalised isogenies, so x_den = h^2 and y_den = h^3, and the
+    device evaluates h alone (h2c.hpp iso11_jac / iso3_jac). Both identities are checked here, coefficient for
+    coefficient: a table for which they fail stops the generation."""
+    assert len(xden) % 2 == 1 and xden[-1] == (1, 0), "x_den is not monic of even degree"
+    d = len(xden) // 2
+    inv2 = (P + 1) // 2
+    h = [(0, 0)] * d + [(1, 0)]
+    for k in range(1, d + 1):
+        s = [0, 0]
+        for i in range(d - k + 1, d):  # h_i h_j with i + j = 2d - k and both strictly between d - k and d
+            t = f2mul(h[i], h[2 * d - k - i])
+            s = [s[0] + t[0], s[1] + t[1]]
+        c = xden[2 * d - k]
+        h[d - k] = ((c[0] - s[0]) * inv2 % P, (c[1] - s[1]) * inv2 % P)
+    h2 = poly_mul(h, h)
+    assert h2 == [(c[0] % P, c[1] % P) for c in xden], "x_den is not the square of a monic polynomial"
+    assert poly_mul(h2, h) == [(c[0] % P, c[1] % P) for c in yden], "y_den is not the cube of x_den's square root"
+    return h
+
+
 def mont(x):
     return (x % P) * MONT % P
 
@@ -415,17 +448,26 @@ def main():
     fp_const("K256", k256)
     fp_const("K256R", k256 * MONT % P)  # mont_mul(raw hi, K256R) = Mont(hi * 2^256)
     fp_const("R2", MONT % P)  # c_fp(R) = R^2 mod p: mont_mul(raw x, R2) = Mont(x)
-    for name, txt in (("ISO11_XNUM", ISO11_XNUM), ("ISO11_XDEN", ISO11_XDEN), ("ISO11_YNUM", ISO11_YNUM),
-                      ("ISO11_YDEN", ISO11_YDEN)):
-        cs = [int(t, 16) for t in txt.split()]
+    # The isogenies are evaluated on their numerators and their kernel polynomial h (x_den = h^2, y_den = h^3:
+    # kernel_poly); the printed denominators above stay the source and get no device table.
+    iso11 = {name: [int(t, 16) for t in txt.split()] for name, txt in (
+        ("XNUM", ISO11_XNUM), ("XDEN", ISO11_XDEN), ("YNUM", ISO11_YNUM), ("YDEN", ISO11_YDEN))}
+    h11 = kernel_poly([(c, 0) for c in iso11["XDEN"]], [(c, 0) for c in iso11["YDEN"]])
+    assert all(c[1] == 0 for c in h11) and len(h11) == 6
+    for name, cs in (("ISO11_XNUM", iso11["XNUM"]), ("ISO11_YNUM", iso11["YNUM"])):
         w("constexpr int %s_LEN = %d;" % (name, len(cs)))
         w("__device__ __constant__ uint32_t %s[%d][12] = {%s};" % (name, len(cs), ", ".join(c_fp(c) for c in cs)))
         # the same coefficients for the lazily reduced 28-bit evaluation (fp28.hpp: c 2^392 mod p, 14 x 28-bit limbs)
         w("__device__ __constant__ uint32_t %s_28[%d][14] = {%s};" % (name, len(cs), ", ".join(c_fp28(c) for c in cs)))
-    for name, cs in (("ISO3_XNUM", ISO3_XNUM), ("ISO3_XDEN", ISO3_XDEN), ("ISO3_YNUM", ISO3_YNUM),
-                     ("ISO3_YDEN", ISO3_YDEN)):
+    w("constexpr int ISO11_H_LEN = %d;  // kernel polynomial: x_den = h^2, y_den = h^3, monic" % len(h11))
+    w("__device__ __constant__ uint32_t ISO11_H_28[%d][14] = {%s};" % (len(h11), ", ".join(c_fp28(c[0]) for c in h11)))
+    h3 = kernel_poly(ISO3_XDEN, ISO3_YDEN)
+    assert len(h3) == 2
+    for name, cs in (("ISO3_XNUM", ISO3_XNUM), ("ISO3_YNUM", ISO3_YNUM)):
         w("constexpr int %s_LEN = %d;" % (name, len(cs)))
         w("__device__ __constant__ uint32_t %s[%d][2][12] = {%s};" % (name, len(cs), ", ".join(c_fp2(c) for c in cs)))
+    w("constexpr int ISO3_H_LEN = %d;  // kernel polynomial x + ISO3_H[0]: x_den = h^2, y_den = h^3" % len(h3))
+    w("__device__ __constant__ uint32_t ISO3_H[%d][2][12] = {%s};" % (len(h3), ", ".join(c_fp2(c) for c in h3)))
     # exponents (plain integers, little-endian 32-bit words)
     for name, e in (("EXP_P_MINUS_2", P - 2), ("EXP_P_PLUS_1_DIV_4", (P + 1) // 4),
                     ("EXP_SR1_C1", sr1_c1), ("EXP_SR2_C3", c3), ("EXP_P_MINUS_1_DIV_2", (P - 1) // 2)):
