@@ -21,6 +21,8 @@ DH_EABANDONED = -7
 DH_ECORRUPT = -8
 DH_ENOBEACON = -9
 DH_NODE_CHECKED = 2
+DH_DEFERRED = 1
+DH_STORE_TRIMMED, DH_STORE_UNTRIMMED, DH_STORE_AUTO = 0, 1, 2
 
 # every symbol declared in include/drandhip.h, with (restype, argtypes)
 _c = ctypes
@@ -69,6 +71,11 @@ SIGNATURES = {
     "dh_store_check_past": (_c.c_int, [_P, _c.c_int, _c.c_char_p, _c.c_size_t, _c.c_uint64, _c.c_size_t, _c.c_uint64, _P,
                                        _c.c_size_t, _P, _P, _P]),
     "dh_store_close": (None, [_P]),
+    "dh_store_open_bolt_format": (_c.c_int, [_P, _c.c_size_t, _c.c_int, _c.POINTER(_P)]),
+    "dh_store_format_stat": (_c.c_int, [_P, _P]),
+    "dh_store_beacons_device": (_c.c_int, [_P, _c.c_uint64, _c.c_uint64, _c.c_size_t, _c.c_size_t, _P, _P, _P, _P, _P, _P,
+                                           _c.c_size_t, _P, _P, _c.c_size_t, _P, _P]),
+    "dh_store_deferred": (_c.c_int, [_P, _c.c_uint64, _c.c_uint64, _P, _c.c_size_t, _P]),
     "dh_profile": (_c.c_int, [_c.c_int]),
     "dh_profile_read": (_c.c_int, [_c.c_char_p, _c.c_size_t]),
     "dh_last_error_string": (_c.c_char_p, []),

@@ -1,6 +1,7 @@
 // Read-only bbolt (go.etcd.io/bbolt, file format v2) page parser shared by the host (plain g++, no HIP) and the
 // device: the trimmed beacon store of chain/boltdb/trimmed.go (bucket "beacons", key = round as 8 bytes big-endian,
-// value = the raw signature), restated from drand_amd/store.py, which it must agree with.
+// value = the raw signature), restated from drand_amd/store.py, which it must agree with; and the value parser of the
+// legacy store of chain/boltdb/store.go (value = hexjson Beacon.Marshal(); hexjson_parse below).
 //
 // Everything is read through bounds-checked little-endian byte accessors over a view {pointer, length}; offsets are
 // 64-bit. A structural defect is an error code (bolt::err), never a read outside the view. The leaf functions take a
@@ -188,6 +189,75 @@ BOLT_HD void bolt_leaf_check(const view& leaf, uint32_t count, uint32_t i0, uint
     info_merge(acc, r, r, 1, 0, e.vsize, 0);
   }
 }
+
+// ---- hexjson values: the legacy store of chain/boltdb/store.go, value = Beacon.Marshal()
+//
+// Only the canonical form is decoded: exactly {"PreviousSig":P,"Round":D,"Signature":S} with nothing before, between
+// or after; P and S are null or a quoted even number (0 allowed) of characters 0-9a-f; D is a decimal of 1-20 digits
+// without a leading zero (0 itself excepted) that fits 64 bits and equals the record's key. Every other value is
+// DEFERRED: nothing is decided about it here, the caller's host decoder does. Offsets are inside the value; the hex
+// lengths count characters (null and "": 0).
+struct hexjson {
+  uint32_t prev_off, prev_hex, sig_off, sig_hex;
+};
+
+BOLT_HD bool hj_lit(const view& v, uint64_t* i, const char* s, uint32_t n) {
+  if (!in(v, *i, n)) return false;
+  for (uint32_t k = 0; k < n; k++)
+    if (v.p[*i + k] != (uint8_t)s[k]) return false;
+  *i += n;
+  return true;
+}
+BOLT_HD bool hj_hex(uint32_t c) { return (c >= '0' && c <= '9') || (c >= 'a' && c <= 'f'); }
+BOLT_HD bool hj_field(const view& v, uint64_t* i, uint32_t* off, uint32_t* hex) {
+  *off = *hex = 0;
+  if (*i >= v.len) return false;
+  if (v.p[*i] == 'n') return hj_lit(v, i, "null", 4);
+  if (v.p[*i] != '"') return false;
+  uint64_t j = *i + 1;
+  while (j < v.len && hj_hex(v.p[j])) j++;
+  if (j >= v.len || v.p[j] != '"' || ((j - *i - 1) & 1)) return false;
+  *off = (uint32_t)(*i + 1);
+  *hex = (uint32_t)(j - *i - 1);
+  *i = j + 1;
+  return true;
+}
+
+BOLT_HD bool hexjson_match(const view& val, uint64_t key, hexjson* out) {
+  if (val.len > 0xffffffffull) return false;
+  uint64_t i = 0;
+  if (!hj_lit(val, &i, "{\"PreviousSig\":", 15) || !hj_field(val, &i, &out->prev_off, &out->prev_hex)) return false;
+  if (!hj_lit(val, &i, ",\"Round\":", 9)) return false;
+  const uint64_t d0 = i;
+  uint64_t r = 0;
+  while (i < val.len && val.p[i] >= '0' && val.p[i] <= '9') {
+    const uint32_t d = val.p[i] - '0';
+    if (i - d0 >= 20 || r > (~0ull - d) / 10) return false;
+    r = r * 10 + d;
+    i++;
+  }
+  if (i == d0 || (i - d0 > 1 && val.p[d0] == '0') || r != key) return false;
+  if (!hj_lit(val, &i, ",\"Signature\":", 13) || !hj_field(val, &i, &out->sig_off, &out->sig_hex)) return false;
+  return hj_lit(val, &i, "}", 1) && i == val.len;
+}
+// true = canonical (and *out is set), false = deferred (*out all zero); reads only inside `val`
+BOLT_HD bool hexjson_parse(const view& val, uint64_t key, hexjson* out) {
+  if (hexjson_match(val, key, out)) return true;
+  out->prev_off = out->prev_hex = out->sig_off = out->sig_hex = 0;
+  return false;
+}
+
+// the byte two validated hex characters at `o` spell
+BOLT_HD uint32_t hj_nib(uint32_t c) { return c <= '9' ? c - '0' : c - 'a' + 10; }
+BOLT_HD uint32_t hj_byte(const view& v, uint64_t o) { return (hj_nib(v.p[o]) << 4) | hj_nib(v.p[o + 1]); }
+
+// What the hexjson scan adds per leaf (16 bytes): deferred round records, the longest decoded Signature / PreviousSig
+struct leaf_json {
+  uint32_t n_deferred, max_sig, max_prev, pad;
+};
+
+// the value of a round element of `leaf`
+BOLT_HD view elem_value(const view& leaf, const elem& e) { return view{leaf.p + e.koff + e.ksize, e.vsize}; }
 
 // a leaf by its byte offset in the file and the bytes it spans
 struct leaf_ref {

@@ -2810,15 +2810,20 @@ struct dh_store {
   size_t len = 0;
   uint32_t page_size = 0;
   uint64_t stat[6] = {0, 0, 0, 0, 0, 0};
+  int format = DH_STORE_TRIMMED;          // fixed at open
+  uint64_t jstat[3] = {0, 0, 0};          // untrimmed: deferred records, longest decoded Signature / PreviousSig
+  std::vector<dh::bolt::leaf_json> jinfo;  // untrimmed: the hexjson scan's table
   std::vector<dh::bolt::leaf_info> info;  // the scan's table, one record per leaf in key order
   std::vector<uint32_t> rleaf;            // the leaves that hold rounds (ascending first / last): the search index
   hipStream_t st = nullptr;
   dbuf d_file, d_leaves, d_info, err, cnt, base, scan_tmp, rounds, rows, lens, miss_prev, gap, moff, missing, verdict, bad;
+  dbuf d_jinfo, prevs, prev_lens, defer;  // untrimmed: rows / lens above hold the decoded Signature column
+  std::vector<uint8_t> h_defer;
   std::vector<uint8_t> h_bad;
   std::vector<uint64_t> h_rounds, h_missing;
   void release() {
     for (dbuf* b : {&d_file, &d_leaves, &d_info, &err, &cnt, &base, &scan_tmp, &rounds, &rows, &lens, &miss_prev, &gap, &moff,
-                    &missing, &verdict, &bad})
+                    &missing, &verdict, &bad, &d_jinfo, &prevs, &prev_lens, &defer})
       b->release();
     if (st) (void)hipStreamDestroy(st);
     st = nullptr;
@@ -2866,7 +2871,33 @@ static int bolt_index(const uint8_t* file, size_t len, dh::bolt::meta* m, std::v
   return DH_OK;
 }
 
-static int store_open(dh_store* s, const uint8_t* file, size_t len) {
+// shouldUseTrimmedBolt (chain/boltdb/store.go:82-110) on the first value of the bucket: a canonical hexjson record ->
+// untrimmed; an empty bucket or any other value -> trimmed, except that a value starting with '{' that is not
+// canonical is not decided here
+static int store_detect(const uint8_t* file, const std::vector<dh::bolt::leaf_ref>& leaves, int* format) {
+  using namespace dh::bolt;
+  *format = DH_STORE_TRIMMED;
+  for (const leaf_ref& lr : leaves) {
+    const view leaf{file + lr.off, lr.ext};
+    uint32_t count = 0;
+    if (bolt_leaf_head(leaf, &count)) return DH_OK;  // the scan names the defect
+    for (uint32_t i = 0; i < count; i++) {
+      elem e;
+      if (bolt_leaf_elem(leaf, i, &e)) return DH_OK;
+      if (e.flags & F_BUCKET) continue;
+      hexjson h;
+      if (e.ksize == 8 && hexjson_parse(elem_value(leaf, e), rd64be(leaf, e.koff), &h)) {
+        *format = DH_STORE_UNTRIMMED;
+      } else if (e.vsize && leaf.p[e.koff + e.ksize] == '{') {
+        return fail(DH_EINVAL, "bbolt store: the first value starts with '{' but is not a canonical hexjson beacon: name the format");
+      }
+      return DH_OK;
+    }
+  }
+  return DH_OK;
+}
+
+static int store_open(dh_store* s, const uint8_t* file, size_t len, int format) {
   using namespace dh::bolt;
   meta m;
   std::vector<leaf_ref> leaves;
@@ -2874,7 +2905,9 @@ static int store_open(dh_store* s, const uint8_t* file, size_t len) {
     prof_wall p("store_index");
     int rc = bolt_index(file, len, &m, &leaves);
     if (rc) return rc;
+    if (format == DH_STORE_AUTO && (rc = store_detect(file, leaves, &format))) return rc;
   }
+  s->format = format;
   int rc = ensure_device();
   if (rc) return rc;
   const size_t nl = leaves.size();
@@ -2918,6 +2951,17 @@ static int store_open(dh_store* s, const uint8_t* file, size_t len) {
   s->stat[3] = n_round ? s->info[s->rleaf.back()].last : 0;
   s->stat[4] = longest;
   s->stat[5] = nl;
+  if (format != DH_STORE_UNTRIMMED) return DH_OK;
+  s->jinfo.resize(nl);
+  HIP_TRY(s->d_jinfo.ensure(nl * sizeof(leaf_json)));
+  HIP_TRY(dh::launch_bolt_scan_json(s->d_file.as<uint8_t>(), s->d_leaves.p, nl, s->d_jinfo.p, s->st));
+  HIP_TRY(hipMemcpyAsync(s->jinfo.data(), s->d_jinfo.p, nl * sizeof(leaf_json), hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));
+  for (const leaf_json& lj : s->jinfo) {
+    s->jstat[0] += lj.n_deferred;
+    s->jstat[1] = std::max<uint64_t>(s->jstat[1], lj.max_sig);
+    s->jstat[2] = std::max<uint64_t>(s->jstat[2], lj.max_prev);
+  }
   return DH_OK;
 }
 
@@ -2979,6 +3023,40 @@ static int store_gather(dh_store* s, size_t lo, size_t nw, size_t total, uint64_
   return DH_OK;
 }
 
+// the untrimmed form of store_gather: c.rounds is required, the other columns as launch_bolt_gather_json takes them
+static int store_gather_json(dh_store* s, size_t lo, size_t nw, size_t total, uint64_t first, uint64_t last, const dh::json_cols& c,
+                             uint64_t* d_missing, size_t nmiss) {
+  if (total + 2 > (size_t)4096 * 4096) return fail(DH_EINVAL, "window of %zu rows: at most 16M rows per call", total);
+  timed_launches tl(s->st);  // resolved after the stream wait below
+  if (total)
+    HIP_TRY(tl.run("k_bolt_gather_json", [&] {
+      return dh::launch_bolt_gather_json(s->d_file.as<uint8_t>(), s->d_leaves.as<dh::bolt::leaf_ref>() + lo, s->base.as<uint32_t>(), nw,
+                                         first, last, c, s->st);
+    }));
+  if (d_missing && nmiss) {
+    HIP_TRY(s->miss_prev.ensure(total + 1));
+    HIP_TRY(s->gap.ensure((total + 1) * 4));
+    HIP_TRY(dh::launch_bolt_link(c.rounds, total, first, last, s->miss_prev.as<uint8_t>(), s->gap.as<uint32_t>(), s->st));
+    HIP_TRY(s->moff.ensure((total + 2) * 4));
+    HIP_TRY(s->scan_tmp.ensure(((total + 1) / 4096 + 2) * 4));
+    HIP_TRY(dh::launch_scan(s->gap.as<uint32_t>(), total + 1, s->moff.as<uint32_t>(), s->scan_tmp.as<uint32_t>(), s->st));
+    HIP_TRY(dh::launch_bolt_fill(c.rounds, total, first, s->moff.as<uint32_t>(), nmiss, d_missing, s->st));
+  }
+  HIP_TRY(hipStreamSynchronize(s->st));
+  return DH_OK;
+}
+
+// the longest decoded Signature / PreviousSig in the leaves [lo, lo + nw)
+static uint32_t window_longest_json(const dh_store* s, size_t lo, size_t nw) {
+  uint32_t m = 0;
+  for (size_t i = lo; i < lo + nw; i++) m = std::max(m, std::max(s->jinfo[i].max_sig, s->jinfo[i].max_prev));
+  return m;
+}
+
+static int store_check_past_json(dh_store* s, int scheme, const uint8_t* pk, size_t pk_len, uint64_t up_to, size_t window,
+                                 uint64_t seed, uint64_t* faulty_out, size_t cap, size_t* n_faulty_out,
+                                 void (*cb)(uint64_t round, uint64_t up_to, void* arg), void* cb_arg);
+
 extern "C" {
 
 int dh_bolt_index(const uint8_t* file, size_t len, uint32_t* page_size_out, uint64_t* leaf_off_out, size_t cap,
@@ -2997,13 +3075,19 @@ int dh_bolt_index(const uint8_t* file, size_t len, uint32_t* page_size_out, uint
 }
 
 int dh_store_open_bolt(const uint8_t* file, size_t len, dh_store** out) {
+  return dh_store_open_bolt_format(file, len, DH_STORE_TRIMMED, out);
+}
+
+int dh_store_open_bolt_format(const uint8_t* file, size_t len, int format, dh_store** out) {
   if (!file || !out) return fail(DH_EINVAL, "null argument");
   *out = nullptr;
+  if (format != DH_STORE_TRIMMED && format != DH_STORE_UNTRIMMED && format != DH_STORE_AUTO)
+    return fail(DH_EINVAL, "unknown store format %d", format);
   if (len > store_max_bytes())
     return fail(DH_ENOMEM, "store file of %zu bytes exceeds DRANDHIP_STORE_MAX_BYTES (%zu): keep the host reader", len,
                 store_max_bytes());
   dh_store* s = new dh_store();
-  int rc = store_open(s, file, len);
+  int rc = store_open(s, file, len, format);
   if (rc) {
     s->release();
     delete s;
@@ -3018,6 +3102,13 @@ int dh_store_open_bolt(const uint8_t* file, size_t len, dh_store** out) {
 int dh_store_stat(const dh_store* s, uint64_t out[6]) {
   if (!s || !out) return fail(DH_EINVAL, "null argument");
   memcpy(out, s->stat, sizeof s->stat);  // fixed at open
+  return DH_OK;
+}
+
+int dh_store_format_stat(const dh_store* s, uint64_t out[4]) {
+  if (!s || !out) return fail(DH_EINVAL, "null argument");
+  out[0] = (uint64_t)s->format;  // fixed at open
+  memcpy(out + 1, s->jstat, sizeof s->jstat);
   return DH_OK;
 }
 
@@ -3071,6 +3162,8 @@ int dh_store_check_past(dh_store* s, int scheme, const uint8_t* pk, size_t pk_le
   int rc = store_enter(s);
   if (rc) return rc;
   *n_faulty_out = 0;
+  if (s->format == DH_STORE_UNTRIMMED)
+    return store_check_past_json(s, scheme, pk, pk_len, up_to, window, seed, faulty_out, cap, n_faulty_out, cb, cb_arg);
   size_t lo, nw, total;
   uint32_t longest;
   // store.Last(): the largest round; the chained Get also needs the record before it (trimmed.go:156-193)
@@ -3147,6 +3240,176 @@ int dh_store_check_past(dh_store* s, int scheme, const uint8_t* pk, size_t pk_le
   }
   *n_faulty_out = nf;
   if (nf > cap) return fail(DH_EINVAL, "%zu faulty rounds, room for %zu", nf, cap);
+  return DH_OK;
+}
+
+}  // extern "C"
+
+// BoltStore's read path (chain/boltdb/store.go:172-210) under the same loop: PreviousSig is the record's own field, so a
+// missing round makes only itself faulty; Last() fails on an empty bucket only. Entered with the handle held.
+static int store_check_past_json(dh_store* s, int scheme, const uint8_t* pk, size_t pk_len, uint64_t up_to, size_t window,
+                                 uint64_t seed, uint64_t* faulty_out, size_t cap, size_t* n_faulty_out,
+                                 void (*cb)(uint64_t round, uint64_t up_to, void* arg), void* cb_arg) {
+  const uint32_t sig_len = (uint32_t)dh_sig_len(scheme);
+  const bool chained = scheme == DH_SCHEME_CHAINED;
+  int rc;
+  size_t lo, nw, total;
+  uint32_t longest;
+  if (!s->stat[1]) return fail(DH_ENOBEACON, "no beacon stored");
+  const uint64_t last_round = s->stat[3];
+  if (s->jstat[0]) {  // Last().Round is the last record's Round field: known here only when the record is canonical
+    if ((rc = store_window(s, last_round, last_round, &lo, &nw, &total, &longest))) return rc;
+    HIP_TRY(s->rounds.ensure(total * 8 + 8));
+    HIP_TRY(s->defer.ensure(total + 8));
+    const dh::json_cols c{s->rounds.as<uint64_t>(), s->defer.as<uint8_t>(), nullptr, nullptr, nullptr, nullptr, 4, 4, total};
+    if ((rc = store_gather_json(s, lo, nw, total, last_round, last_round, c, nullptr, 0))) return rc;
+    uint8_t d = 0;
+    if (total) HIP_TRY(hipMemcpy(&d, s->defer.p, 1, hipMemcpyDeviceToHost));
+    if (d)
+      return fail(DH_EINVAL, "the last record (key %llu) is not canonical hexjson: Last() needs the host decoder",
+                  (unsigned long long)last_round);
+  }
+  if (last_round < up_to) up_to = last_round;
+  const uint64_t store_len = s->stat[0];
+  if (store_len <= 1) return DH_OK;
+  const uint64_t hi = std::min<uint64_t>(store_len - 1, std::max<uint64_t>(up_to, 1));  // the loop's i < len and i >= up_to
+  size_t nf = 0, ndef = 0;
+  auto emit = [&](uint64_t r) {
+    if (nf < cap) faulty_out[nf] = r;
+    nf++;
+  };
+  for (uint64_t a = 1; a <= hi;) {
+    const uint64_t b = hi - a < window - 1 ? hi : a + (window - 1);
+    if (cb) cb(a, up_to, cb_arg);
+    size_t nmiss, stride;
+    {
+      prof_wall p("store_gather_link");
+      if ((rc = store_window(s, a, b, &lo, &nw, &total, &longest))) return rc;
+      const uint32_t longest_dec = window_longest_json(s, lo, nw);
+      stride = ((size_t)std::max(sig_len, longest_dec) + 3) & ~(size_t)3;
+      if (stride > 65536)
+        return fail(DH_EINVAL, "row stride %zu above 64 KiB (a %u-byte field in rounds %llu..%llu): keep the host reader", stride,
+                    longest_dec, (unsigned long long)a, (unsigned long long)b);
+      nmiss = window_missing(a, b, total);
+      HIP_TRY(s->rounds.ensure(total * 8 + 8));
+      HIP_TRY(s->rows.ensure(total * stride + 8));
+      HIP_TRY(s->lens.ensure(total * 4 + 4));
+      HIP_TRY(s->defer.ensure(total + 8));
+      if (chained) {
+        HIP_TRY(s->prevs.ensure(total * stride + 8));
+        HIP_TRY(s->prev_lens.ensure(total * 4 + 4));
+      }
+      HIP_TRY(s->missing.ensure(nmiss * 8 + 8));
+      const dh::json_cols c{s->rounds.as<uint64_t>(), s->defer.as<uint8_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
+                            chained ? s->prevs.as<uint8_t>() : nullptr, chained ? s->prev_lens.as<uint32_t>() : nullptr,
+                            (uint32_t)stride, (uint32_t)stride, total};
+      if ((rc = store_gather_json(s, lo, nw, total, a, b, c, s->missing.as<uint64_t>(), nmiss))) return rc;
+    }
+    if (total) {
+      prof_wall p("store_verify");
+      HIP_TRY(s->verdict.ensure(total));
+      // a deferred row is verified as the all-zero record it was left as, and its verdict is not read
+      rc = dh_verify_batch_device(scheme, pk, pk_len, s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(), stride,
+                                  chained ? s->prevs.as<uint8_t>() : nullptr, stride, chained ? s->prev_lens.as<uint32_t>() : nullptr,
+                                  total, s->verdict.as<uint8_t>(), nullptr, seed, nullptr, nullptr);
+      if (rc) return rc;
+    }
+    s->h_bad.resize(total);
+    s->h_defer.resize(total);
+    s->h_rounds.resize(total);
+    s->h_missing.resize(nmiss);
+    if (total) {
+      HIP_TRY(s->bad.ensure(total));
+      HIP_TRY(dh::launch_bolt_fold_json(s->lens.as<uint32_t>(), s->defer.as<uint8_t>(), s->verdict.as<uint8_t>(), total, sig_len,
+                                        s->bad.as<uint8_t>(), s->st));
+      HIP_TRY(hipMemcpyAsync(s->h_bad.data(), s->bad.p, total, hipMemcpyDeviceToHost, s->st));
+      HIP_TRY(hipMemcpyAsync(s->h_defer.data(), s->defer.p, total, hipMemcpyDeviceToHost, s->st));
+      HIP_TRY(hipMemcpyAsync(s->h_rounds.data(), s->rounds.p, total * 8, hipMemcpyDeviceToHost, s->st));
+    }
+    if (nmiss) HIP_TRY(hipMemcpyAsync(s->h_missing.data(), s->missing.p, nmiss * 8, hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));
+    size_t im = 0;
+    for (size_t i = 0; i < total; i++) {
+      ndef += s->h_defer[i];
+      if (!s->h_bad[i]) continue;
+      while (im < nmiss && s->h_missing[im] < s->h_rounds[i]) emit(s->h_missing[im++]);
+      emit(s->h_rounds[i]);
+    }
+    while (im < nmiss) emit(s->h_missing[im++]);
+    if (b == hi) break;
+    a = b + 1;
+  }
+  *n_faulty_out = nf;
+  if (nf > cap) return fail(DH_EINVAL, "%zu faulty rounds, room for %zu", nf, cap);
+  return ndef ? DH_DEFERRED : DH_OK;
+}
+
+extern "C" {
+
+int dh_store_beacons_device(dh_store* s, uint64_t first, uint64_t last, size_t sig_stride, size_t prev_stride, uint64_t* d_rounds,
+                            uint8_t* d_sigs, uint32_t* d_sig_lens, uint8_t* d_prevs, uint32_t* d_prev_lens, uint8_t* d_deferred,
+                            size_t cap_rows, size_t* n_rows_out, uint64_t* d_missing, size_t cap_missing, size_t* n_missing_out,
+                            void* hip_stream) {
+  if (!s || !n_rows_out) return fail(DH_EINVAL, "null argument");
+  const bool want_prev = d_prevs || d_prev_lens;
+  if (!sig_stride || (sig_stride & 3) || sig_stride > ((size_t)1 << 20) ||
+      (want_prev && (!prev_stride || (prev_stride & 3) || prev_stride > ((size_t)1 << 20))))
+    return fail(DH_EINVAL, "row strides %zu / %zu: positive multiples of 4, at most 1 MiB", sig_stride, prev_stride);
+  if (!d_prevs != !d_prev_lens) return fail(DH_EINVAL, "d_prevs and d_prev_lens are given together or not at all");
+  store_guard g(s);
+  int rc = store_enter(s);
+  if (rc) return rc;
+  if (s->format != DH_STORE_UNTRIMMED) return fail(DH_EINVAL, "not an untrimmed (hexjson) store: dh_store_columns_device serves it");
+  prof_wall p("store_gather_link");
+  if (hip_stream) HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));  // the output buffers may be in use there
+  size_t lo, nw, total;
+  uint32_t longest;
+  if ((rc = store_window(s, first, last, &lo, &nw, &total, &longest))) return rc;
+  const size_t nmiss = window_missing(first, last, total);
+  *n_rows_out = total;
+  if (n_missing_out) *n_missing_out = nmiss;
+  if (total > cap_rows || (d_missing && nmiss > cap_missing))
+    return fail(DH_EINVAL, "%zu rows and %zu missing rounds, room for %zu and %zu", total, nmiss, cap_rows, d_missing ? cap_missing : 0);
+  if (total && (!d_rounds || !d_sigs || !d_sig_lens || !d_deferred)) return fail(DH_EINVAL, "null output");
+  if (d_missing && nmiss > 0xffffffffull) return fail(DH_EINVAL, "%zu missing rounds", nmiss);
+  if (!total && !(d_missing && nmiss)) return DH_OK;
+  uint64_t* rounds = d_rounds;
+  if (!rounds) {  // no row: the gaps are still counted from a rounds column
+    HIP_TRY(s->rounds.ensure(8));
+    rounds = s->rounds.as<uint64_t>();
+  }
+  const dh::json_cols c{rounds, d_deferred, d_sigs, d_sig_lens, d_prevs, d_prev_lens, (uint32_t)sig_stride,
+                        (uint32_t)(want_prev ? prev_stride : 4), cap_rows};
+  return store_gather_json(s, lo, nw, total, first, last, c, d_missing, nmiss);
+}
+
+int dh_store_deferred(dh_store* s, uint64_t first, uint64_t last, uint64_t* out, size_t cap, size_t* n_out) {
+  if (!s || !n_out || (cap && !out)) return fail(DH_EINVAL, "null argument");
+  store_guard g(s);
+  int rc = store_enter(s);
+  if (rc) return rc;
+  *n_out = 0;
+  if (s->format != DH_STORE_UNTRIMMED || !s->jstat[0]) return DH_OK;  // a trimmed store defers nothing
+  size_t lo, nw, total;
+  uint32_t longest;
+  if ((rc = store_window(s, first, last, &lo, &nw, &total, &longest))) return rc;
+  if (!total) return DH_OK;
+  HIP_TRY(s->rounds.ensure(total * 8 + 8));
+  HIP_TRY(s->defer.ensure(total + 8));
+  const dh::json_cols c{s->rounds.as<uint64_t>(), s->defer.as<uint8_t>(), nullptr, nullptr, nullptr, nullptr, 4, 4, total};
+  if ((rc = store_gather_json(s, lo, nw, total, first, last, c, nullptr, 0))) return rc;
+  s->h_defer.resize(total);
+  s->h_rounds.resize(total);
+  HIP_TRY(hipMemcpy(s->h_defer.data(), s->defer.p, total, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(s->h_rounds.data(), s->rounds.p, total * 8, hipMemcpyDeviceToHost));
+  size_t n = 0;
+  for (size_t i = 0; i < total; i++) {
+    if (!s->h_defer[i]) continue;
+    if (n < cap) out[n] = s->h_rounds[i];
+    n++;
+  }
+  *n_out = n;
+  if (n > cap) return fail(DH_EINVAL, "%zu deferred records, room for %zu", n, cap);
   return DH_OK;
 }
 

@@ -7,6 +7,8 @@
 //   k_bolt_gather  one wave per leaf of a window: rounds / lens / value rows at base[leaf] + rank, in key order
 //   k_bolt_link    per row: is the predecessor row round - 1; the gaps of [first, last] (then launch_scan, k_bolt_fill)
 //   k_bolt_fold    per row: faulty = predecessor missing | stored length != signature length | verdict 0
+// The legacy hexjson store (§18) adds k_bolt_scan_json (deferred records, longest decoded fields per leaf),
+// k_bolt_gather_json (the hex-decoded Signature / PreviousSig rows) and k_bolt_fold_json (no predecessor term).
 // Memory-bound and small next to verification; plain C++, no atomics on the output order.
 #include <hip/hip_runtime.h>
 
@@ -144,6 +146,123 @@ __global__ __launch_bounds__(64) void k_bolt_gather(const uint8_t* __restrict__ 
   }
 }
 
+// ---- the legacy hexjson store: the same walk, the values decoded by bolt.hpp's hexjson_parse
+
+// a leaf of up to LDS_LEAF bytes, 16-byte aligned at both ends, is copied to `lds` and viewed there; others in place
+__device__ __forceinline__ view stage_leaf(const uint8_t* __restrict__ file, const leaf_ref lr, uint4* lds) {
+  if (lr.ext <= LDS_LEAF && !(lr.off & 15) && !(lr.ext & 15)) {
+    const uint4* src = (const uint4*)(file + lr.off);
+    for (uint32_t i = threadIdx.x; i < (uint32_t)(lr.ext / 16); i += 64) lds[i] = src[i];
+    __syncthreads();
+    return view{(const uint8_t*)lds, lr.ext};
+  }
+  return view{file + lr.off, lr.ext};
+}
+
+// after k_bolt_scan: per leaf, the deferred round records and the longest decoded Signature / PreviousSig (bytes)
+__global__ __launch_bounds__(64) void k_bolt_scan_json(const uint8_t* __restrict__ file, const leaf_ref* __restrict__ leaves,
+                                                       leaf_json* __restrict__ out) {
+  __shared__ uint4 lds[LDS_LEAF / 16];
+  __shared__ leaf_json sh[64];
+  const uint32_t lane = threadIdx.x;
+  const view v = stage_leaf(file, leaves[blockIdx.x], lds);
+  leaf_json acc{0, 0, 0, 0};
+  uint32_t count = 0;
+  if (bolt_leaf_head(v, &count)) count = 0;
+  for (uint32_t i = lane; i < count; i += 64) {
+    elem e;
+    if (bolt_leaf_elem(v, i, &e) || !is_round(e)) continue;
+    hexjson h;
+    if (!hexjson_parse(elem_value(v, e), rd64be(v, e.koff), &h)) {
+      acc.n_deferred++;
+      continue;
+    }
+    if (h.sig_hex / 2 > acc.max_sig) acc.max_sig = h.sig_hex / 2;
+    if (h.prev_hex / 2 > acc.max_prev) acc.max_prev = h.prev_hex / 2;
+  }
+  sh[lane] = acc;
+  __syncthreads();
+  if (lane == 0) {
+    leaf_json t{0, 0, 0, 0};
+    for (int k = 0; k < 64; k++) {
+      t.n_deferred += sh[k].n_deferred;
+      if (sh[k].max_sig > t.max_sig) t.max_sig = sh[k].max_sig;
+      if (sh[k].max_prev > t.max_prev) t.max_prev = sh[k].max_prev;
+    }
+    out[blockIdx.x] = t;
+  }
+}
+
+// the chunk's rows are consecutive in the output: lane t writes dword t of them, decoded from 8 hex characters
+__device__ __forceinline__ void write_hex_rows(const view v, uint8_t* __restrict__ rows, uint32_t stride, uint64_t run, uint32_t nsel,
+                                               uint64_t cap_rows, const uint64_t* sel_off, const uint32_t* sel_hex) {
+  const uint32_t dw = stride / 4;
+  for (uint32_t t = threadIdx.x; t < nsel * dw; t += 64) {
+    const uint32_t s = t / dw, w = t - s * dw;
+    const uint64_t row = run + s;
+    if (row >= cap_rows) continue;
+    const uint32_t nb = sel_hex[s] / 2;
+    uint32_t word = 0;
+    if (nb <= stride) {  // a longer value leaves the row zero, never a prefix
+      const uint64_t k = sel_off[s] + 8 * (uint64_t)w;
+      for (uint32_t j = 0; j < 4; j++)
+        if (4 * w + j < nb) word |= hj_byte(v, k + 2 * j) << (8 * j);
+    }
+    ((uint32_t*)rows)[row * dw + w] = word;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_bolt_gather_json(const uint8_t* __restrict__ file, const leaf_ref* __restrict__ leaves,
+                                                         const uint32_t* __restrict__ base, uint64_t first, uint64_t last,
+                                                         const json_cols c) {
+  __shared__ uint4 lds[LDS_LEAF / 16];
+  __shared__ uint64_t sig_off[64], prev_off[64];
+  __shared__ uint32_t sig_hex[64], prev_hex[64];
+  const uint32_t lane = threadIdx.x;
+  if (base[blockIdx.x + 1] == base[blockIdx.x]) return;  // no row of the window in this leaf
+  uint64_t run = base[blockIdx.x];
+  const view v = stage_leaf(file, leaves[blockIdx.x], lds);
+  uint32_t count = 0;
+  if (bolt_leaf_head(v, &count)) return;
+  for (uint32_t c0 = 0; c0 < count; c0 += 64) {
+    elem e;
+    uint64_t r = 0;
+    hexjson h{0, 0, 0, 0};
+    const bool take = pick(v, c0 + lane, count, first, last, &e, &r);
+    const bool canon = take && hexjson_parse(elem_value(v, e), r, &h);
+    const uint64_t m = __ballot(take);
+    const uint32_t rank = __popcll(m & ((1ull << lane) - 1)), nsel = __popcll(m);
+    if (take) {
+      const uint64_t row = run + rank;
+      if (row < c.cap_rows) {  // a deferred record: zero lengths and (below) zero rows
+        c.rounds[row] = r;
+        c.deferred[row] = !canon;
+        if (c.sig_lens) c.sig_lens[row] = h.sig_hex / 2;
+        if (c.prev_lens) c.prev_lens[row] = h.prev_hex / 2;
+      }
+      sig_off[rank] = e.koff + 8 + h.sig_off;
+      sig_hex[rank] = h.sig_hex;
+      prev_off[rank] = e.koff + 8 + h.prev_off;
+      prev_hex[rank] = h.prev_hex;
+    }
+    __syncthreads();
+    if (c.sigs) write_hex_rows(v, c.sigs, c.sig_stride, run, nsel, c.cap_rows, sig_off, sig_hex);
+    if (c.prevs) write_hex_rows(v, c.prevs, c.prev_stride, run, nsel, c.cap_rows, prev_off, prev_hex);
+    __syncthreads();
+    run += nsel;
+  }
+}
+
+// the hexjson store's fold: the stored PreviousSig was verified with the row, so there is no predecessor term; a
+// deferred row is not decided here
+__global__ __launch_bounds__(256) void k_bolt_fold_json(const uint32_t* __restrict__ sig_lens, const uint8_t* __restrict__ deferred,
+                                                        const uint8_t* __restrict__ verdict, size_t n, uint32_t sig_len,
+                                                        uint8_t* __restrict__ bad) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  bad[i] = !deferred[i] && (sig_lens[i] != sig_len || !verdict[i]);
+}
+
 // slot i of n + 1: the rounds of [first, last] missing before row i (slot n: after the last row)
 __global__ __launch_bounds__(256) void k_bolt_link(const uint64_t* __restrict__ rounds, size_t n, uint64_t first, uint64_t last,
                                                    uint8_t* __restrict__ miss_prev, uint32_t* __restrict__ gap) {
@@ -221,6 +340,21 @@ hipError_t launch_bolt_fill(const uint64_t* rounds, size_t n, uint64_t first, co
 hipError_t launch_bolt_fold(const uint64_t* rounds, const uint32_t* lens, const uint8_t* miss_prev, const uint8_t* verdict, size_t n,
                             uint32_t sig_len, int prev_layout, uint64_t a, uint8_t* bad, hipStream_t st) {
   if (n) hipLaunchKernelGGL(k_bolt_fold, dim3(nblk(n, 256)), dim3(256), 0, st, rounds, lens, miss_prev, verdict, n, sig_len, prev_layout, a, bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_bolt_scan_json(const uint8_t* file, const void* leaves, size_t n, void* jinfo, hipStream_t st) {
+  if (n) hipLaunchKernelGGL(k_bolt_scan_json, dim3((unsigned)n), dim3(64), 0, st, file, (const leaf_ref*)leaves, (leaf_json*)jinfo);
+  return hipGetLastError();
+}
+hipError_t launch_bolt_gather_json(const uint8_t* file, const void* leaves, const uint32_t* base, size_t n, uint64_t first,
+                                   uint64_t last, const json_cols& c, hipStream_t st) {
+  if (n) hipLaunchKernelGGL(k_bolt_gather_json, dim3((unsigned)n), dim3(64), 0, st, file, (const leaf_ref*)leaves, base, first, last, c);
+  return hipGetLastError();
+}
+hipError_t launch_bolt_fold_json(const uint32_t* sig_lens, const uint8_t* deferred, const uint8_t* verdict, size_t n, uint32_t sig_len,
+                                 uint8_t* bad, hipStream_t st) {
+  if (n) hipLaunchKernelGGL(k_bolt_fold_json, dim3(nblk(n, 256)), dim3(256), 0, st, sig_lens, deferred, verdict, n, sig_len, bad);
   return hipGetLastError();
 }
 

@@ -260,6 +260,26 @@ hipError_t launch_bolt_fill(const uint64_t* rounds, size_t n, uint64_t first, co
 hipError_t launch_bolt_fold(const uint64_t* rounds, const uint32_t* lens, const uint8_t* miss_prev, const uint8_t* verdict, size_t n,
                             uint32_t sig_len, int prev_layout, uint64_t a, uint8_t* bad, hipStream_t st);
 
+// The legacy hexjson store. scan_json: one leaf_json (16 bytes) per leaf. gather_json: for the window's
+// rows at base[leaf] + rank, rounds, deferred (1 = the value is not canonical hexjson: zero row, zero lengths) and the
+// hex-decoded Signature / PreviousSig rows (strides multiples of 4; sigs + sig_lens and prevs + prev_lens nullable).
+// fold_json: bad[row] = not deferred and (decoded length != sig_len or verdict 0).
+struct json_cols {
+  uint64_t* rounds;
+  uint8_t* deferred;
+  uint8_t* sigs;
+  uint32_t* sig_lens;
+  uint8_t* prevs;
+  uint32_t* prev_lens;
+  uint32_t sig_stride, prev_stride;
+  uint64_t cap_rows;
+};
+hipError_t launch_bolt_scan_json(const uint8_t* file, const void* leaves, size_t n, void* jinfo, hipStream_t st);
+hipError_t launch_bolt_gather_json(const uint8_t* file, const void* leaves, const uint32_t* base, size_t n, uint64_t first,
+                                   uint64_t last, const json_cols& c, hipStream_t st);
+hipError_t launch_bolt_fold_json(const uint32_t* sig_lens, const uint8_t* deferred, const uint8_t* verdict, size_t n, uint32_t sig_len,
+                                 uint8_t* bad, hipStream_t st);
+
 #ifdef DH_COUNT_PRODUCTS
 // counting build: field products executed since the last take, per translation unit (fp_mul28.hpp)
 hipError_t count_take_prep(unsigned long long* v);

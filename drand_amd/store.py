@@ -13,6 +13,8 @@ store file, plus columns(first, last) for bulk ingestion.
 * DeviceBoltStore — the trimmed layout parsed on the device (libdrandhip dh_store_*): the file image
   is uploaded once, columns(first, last) come out in device memory in the layout dh_verify_batch_device takes, and
   check_past_beacons over it is one library call. It agrees with BoltTrimmedStore on every file both accept.
+  With fmt="untrimmed" (or "auto" on such a file) it reads the legacy layout the same way and agrees
+  with BoltUntrimmedStore; records that are not canonical hexjson are decoded here, by beacon_from_hexjson.
 * hexjson records: client.RandomData {"round","randomness","signature","previous_signature"}
   (/root/reference/client/random.go:5-25) and BeaconPacket-shaped JSON, one object per line or a JSON list.
 """
@@ -188,13 +190,27 @@ class DeviceBoltStore:
     """trimmedStore read path (chain/boltdb/trimmed.go:156-193 of the reference) with the bbolt file parsed on the
     device: len / last / columns like BoltTrimmedStore, columns_device for tensors that stay in device memory, and
     check_past (what sync.check_past_beacons calls for this store type): SyncManager.CheckPastBeacons in one
-    dh_store_check_past call. A structurally invalid file raises BoltError from open(), as BoltFile does."""
+    dh_store_check_past call. A structurally invalid file raises BoltError from open(), as BoltFile does.
 
-    def __init__(self, path, requires_previous, open_now=True):
+    Untrimmed stores (fmt="untrimmed", or "auto" on a file whose first value is a canonical hexjson beacon): the
+    BoltStore read path (chain/boltdb/store.go:172-210) and what BoltUntrimmedStore returns. The device decodes the
+    canonical records ({"PreviousSig":P,"Round":D,"Signature":S}, lowercase hex, Round equal to the key); every other
+    record is deferred to the host, where beacon_from_hexjson decides it. That function is this project's restatement
+    of Beacon.Unmarshal, not a decoder pinned to nikkolasg/hexjson: a verdict on a deferred record is the
+    restatement's. Stores written by drand hold canonical records only."""
+
+    FORMATS = {"trimmed": _lib.DH_STORE_TRIMMED, "untrimmed": _lib.DH_STORE_UNTRIMMED, "auto": _lib.DH_STORE_AUTO}
+
+    def __init__(self, path, requires_previous, open_now=True, fmt="trimmed"):
+        if fmt not in self.FORMATS:
+            raise ValueError("fmt %r: one of %s" % (fmt, sorted(self.FORMATS)))
         self.path = path
         self.requires_previous = bool(requires_previous)
+        self.fmt = fmt
+        self.untrimmed = None  # known once open
         self._h = None
         self._stat = None
+        self._jstat = None
         if open_now:
             self.open()
 
@@ -205,12 +221,20 @@ class DeviceBoltStore:
         lib = _lib.load()
         data = np.fromfile(self.path, dtype=np.uint8)
         h = ctypes.c_void_p()
-        rc = lib.dh_store_open_bolt(ctypes.c_void_p(data.ctypes.data), data.size, ctypes.byref(h))
+        if self.fmt == "trimmed":
+            rc = lib.dh_store_open_bolt(ctypes.c_void_p(data.ctypes.data), data.size, ctypes.byref(h))
+        else:
+            rc = lib.dh_store_open_bolt_format(ctypes.c_void_p(data.ctypes.data), data.size, self.FORMATS[self.fmt],
+                                               ctypes.byref(h))
         self._raise(rc)
         self._h = h
         st = (ctypes.c_uint64 * 6)()
         self._raise(lib.dh_store_stat(h, st))
         self._stat = [int(x) for x in st]
+        js = (ctypes.c_uint64 * 4)()
+        self._raise(lib.dh_store_format_stat(h, js))
+        self._jstat = [int(x) for x in js]
+        self.untrimmed = self._jstat[0] == _lib.DH_STORE_UNTRIMMED
         return self
 
     def close(self):
@@ -263,6 +287,8 @@ class DeviceBoltStore:
 
     def get(self, round_):
         round_ = int(round_)
+        if self.untrimmed:
+            return beacon_from_hexjson(self._raw(round_))
         lo = round_ - 1 if self.requires_previous and round_ > 0 else round_
         rounds, rows, lens, _ = self._columns_host(lo, round_)
         have = {int(r): rows[i, :lens[i]].tobytes() for i, r in enumerate(rounds)}
@@ -308,8 +334,11 @@ class DeviceBoltStore:
                 missing.cpu().numpy().view(np.uint64))
 
     def columns(self, first, last, sig_len):
-        """The tuple of BoltTrimmedStore.columns, from the device columns copied back."""
+        """The tuple of BoltTrimmedStore.columns, from the device columns copied back. Untrimmed: the same tuple over
+        BoltUntrimmedStore.get (the stored PreviousSig; a record the host decoder rejects counts as missing)."""
         first, last = int(first), int(last)
+        if self.untrimmed:
+            return self._columns_untrimmed(first, last, sig_len)
         lo = first - 1 if self.requires_previous and first > 0 else first
         rounds, rows, lens, missing = self._columns_host(lo, last, sig_len)
         keep = rounds >= first
@@ -332,9 +361,118 @@ class DeviceBoltStore:
         miss = sorted(set(int(r) for r in missing if r >= first) | set(int(r) for r in lost))
         return rounds[idx].astype(np.uint64), sig_arr, prevs, miss
 
+    # ---- untrimmed stores
+    def format_stat(self):
+        """{"format", "deferred", "longest_signature", "longest_previous"} (dh_store_format_stat)."""
+        return dict(zip(("format", "deferred", "longest_signature", "longest_previous"),
+                        [["trimmed", "untrimmed"][self._jstat[0]]] + self._jstat[1:]))
+
+    def _raw(self, round_):
+        rounds, rows, lens, _ = self._columns_host(round_, round_)
+        if not len(rounds):
+            raise NoBeaconStored(round_)
+        return rows[0, :lens[0]].tobytes()
+
+    def beacons_device(self, first, last, sig_stride=None, prev_stride=None, want_prev=True):
+        """Rounds first..last of an untrimmed store, decoded, in device memory: (rounds int64[n], sigs uint8[n, sig_stride],
+        sig_lens int32[n], prevs uint8[n, prev_stride] | None, prev_lens int32[n] | None, deferred uint8[n],
+        missing int64[m]) torch tensors in the layout dh_verify_batch_device takes. Strides default to the store's longest
+        decoded field rounded up to 4. A deferred row is all zero with zero lengths."""
+        import torch
+        lib = _lib.load()
+        sig_stride = int(sig_stride or max(4, (self._jstat[2] + 3) & ~3))
+        prev_stride = int(prev_stride or max(4, (self._jstat[3] + 3) & ~3))
+        first, last = int(first), int(last)
+        n, m = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        rc = lib.dh_store_beacons_device(self._h, first, last, sig_stride, prev_stride, None, None, None, None, None, None, 0,
+                                         ctypes.byref(n), None, 0, ctypes.byref(m), None)
+        if rc != _lib.DH_EINVAL or not n.value:  # DH_EINVAL with the sizes needed, unless the window holds no row
+            self._raise(rc)
+        dev = torch.device("cuda")
+        rounds = torch.empty(n.value, dtype=torch.int64, device=dev)
+        sigs = torch.empty((n.value, sig_stride), dtype=torch.uint8, device=dev)
+        sig_lens = torch.empty(n.value, dtype=torch.int32, device=dev)
+        prevs = torch.empty((n.value, prev_stride), dtype=torch.uint8, device=dev) if want_prev else None
+        prev_lens = torch.empty(n.value, dtype=torch.int32, device=dev) if want_prev else None
+        deferred = torch.empty(n.value, dtype=torch.uint8, device=dev)
+        missing = torch.empty(m.value, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize()
+        self._raise(lib.dh_store_beacons_device(
+            self._h, first, last, sig_stride, prev_stride, rounds.data_ptr(), sigs.data_ptr(), sig_lens.data_ptr(),
+            prevs.data_ptr() if want_prev else None, prev_lens.data_ptr() if want_prev else None, deferred.data_ptr(), n.value,
+            ctypes.byref(n), missing.data_ptr(), m.value, ctypes.byref(m), None))
+        return rounds, sigs, sig_lens, prevs, prev_lens, deferred, missing
+
+    def deferred(self, first=0, last=(1 << 64) - 1):
+        """Keys of the records in first..last that the device leaves to the host decoder (dh_store_deferred)."""
+        lib = _lib.load()
+        cap = max(1, self._jstat[1])
+        out = np.zeros(cap, np.uint64)
+        n = ctypes.c_size_t(0)
+        self._raise(lib.dh_store_deferred(self._h, int(first), int(last), ctypes.c_void_p(out.ctypes.data), cap, ctypes.byref(n)))
+        return [int(x) for x in out[:n.value]]
+
+    def _columns_untrimmed(self, first, last, sig_len):
+        rounds, sigs, sig_lens, prevs, prev_lens, deferred, missing = self.beacons_device(first, last)
+        rounds, sigs, sig_lens = rounds.cpu().numpy().view(np.uint64), sigs.cpu().numpy(), sig_lens.cpu().numpy()
+        prevs, prev_lens, deferred = prevs.cpu().numpy(), prev_lens.cpu().numpy(), deferred.cpu().numpy()
+        out_r, out_s, out_p = [], [], []
+        miss = [int(r) for r in missing.cpu().numpy().view(np.uint64)]
+        for i, r in enumerate(rounds):
+            if deferred[i]:  # decided by the host decoder
+                try:
+                    b = beacon_from_hexjson(self._raw(int(r)))
+                except DECODE_ERRORS:
+                    miss.append(int(r))
+                    continue
+                rnd, sig, prev = b.round, b.signature, b.previous_signature
+            else:
+                rnd, sig, prev = int(r), sigs[i, :sig_lens[i]].tobytes(), prevs[i, :prev_lens[i]].tobytes()
+            out_r.append(rnd)
+            row = np.zeros(sig_len, np.uint8)
+            if len(sig) == sig_len:
+                row[:] = np.frombuffer(sig, np.uint8)
+            out_s.append(row)
+            out_p.append(prev)
+        sig_arr = np.array(out_s, dtype=np.uint8).reshape(-1, sig_len)
+        return np.array(out_r, dtype=np.uint64), sig_arr, out_p if self.requires_previous else None, sorted(miss)
+
+    def _resolve_deferred(self, scheme, pubkey, up_to, seed):
+        """[(key, reported round)] of the faulty ones among the deferred records the CheckPastBeacons loop visits: a
+        value beacon_from_hexjson rejects is faulty under its key (the Get error, sync_manager.go:205-212); a decoded
+        one is verified and reported under its Round field (:215-217)."""
+        last = self._stat[3]
+        up_to = min(int(up_to), last)
+        hi = min(self._stat[0] - 1, max(up_to, 1))
+        out, pend = [], []
+        for k in (self.deferred(1, hi) if hi >= 1 else []):
+            try:
+                pend.append((k, beacon_from_hexjson(self._raw(k))))
+            except DECODE_ERRORS:
+                out.append((k, k))
+        if pend:
+            rounds = np.array([b.round for _, b in pend], dtype=np.uint64)
+            sigs = np.zeros((len(pend), scheme.sig_len), dtype=np.uint8)
+            bad_len = np.zeros(len(pend), dtype=bool)
+            for i, (_, b) in enumerate(pend):
+                if len(b.signature) == scheme.sig_len:
+                    sigs[i] = np.frombuffer(b.signature, dtype=np.uint8)
+                else:
+                    bad_len[i] = True
+            prevs = [b.previous_signature for _, b in pend] if scheme.chained else None
+            ok, _ = scheme.verify_beacons(pubkey, rounds, sigs, prevs, seed=seed, want_randomness=False)
+            out += [(k, b.round) for (k, b), v, bl in zip(pend, ok, bad_len) if bl or not v]
+        return out
+
     def check_past(self, scheme, pubkey, up_to, cb=None, window=1 << 20, seed=0):
         """dh_store_check_past: the faulty rounds of sync.check_past_beacons over this store. cb(round, up_to) is
-        called once per window. Raises StrideTooLarge when the library asks for the host path."""
+        called once per window. Raises StrideTooLarge when the library asks for the host path.
+
+        Untrimmed stores: the library skips the records that are not canonical hexjson (DH_DEFERRED); those are
+        decided HERE, by this module's restatement of the decoder (beacon_from_hexjson), not by a decoder pinned to
+        nikkolasg/hexjson, verified in one small scheme.verify_beacons call and merged into the device's list at the
+        position of their key. A deferred last record is a ValueError (Last().Round needs the host decoder: use
+        BoltUntrimmedStore)."""
         lib = _lib.load()
         hook = _CB((lambda r, u, _a: cb(int(r), int(u))) if cb is not None else (lambda r, u, _a: None))
         cap = max(1, self.len())  # the rounds examined lie below len(): one call always has room
@@ -350,7 +488,11 @@ class DeviceBoltStore:
             if rc == _lib.DH_EINVAL and "64 KiB" in _lib.last_error():
                 raise StrideTooLarge(_lib.last_error())
             self._raise(rc)
-            return [int(x) for x in out[:n.value]]
+            got = [int(x) for x in out[:n.value]]
+            if rc == _lib.DH_DEFERRED:
+                extra = self._resolve_deferred(scheme, pubkey, up_to, seed)
+                got = [rep for _k, rep in sorted([(k, k) for k in got] + extra, key=lambda t: t[0])]
+            return got
 
 
 class BoltUntrimmedStore(_BoltStoreBase):
@@ -361,6 +503,23 @@ class BoltUntrimmedStore(_BoltStoreBase):
         if v is None:
             raise NoBeaconStored(round_)
         return beacon_from_hexjson(v)
+
+
+# what beacon_from_hexjson raises on a value it does not decode (bad JSON / hex, or JSON of another shape)
+DECODE_ERRORS = (ValueError, TypeError, AttributeError)
+
+
+def looks_untrimmed(path):
+    """shouldUseTrimmedBolt (/root/reference/chain/boltdb/store.go:82-110), negated: the first value of the bucket
+    decodes as a hexjson beacon."""
+    kv = BoltFile(path).bucket(BEACON_BUCKET)
+    if not kv:
+        return False
+    try:
+        beacon_from_hexjson(kv[min(kv)])
+    except DECODE_ERRORS:
+        return False
+    return True
 
 
 def _hexbytes(x):

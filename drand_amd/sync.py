@@ -62,13 +62,17 @@ def check_past_beacons(store, scheme, pubkey, up_to, cb=None, window=1 << 20, se
     """Faulty rounds (ascending) among the stored rounds 1 .. min(up_to, last); [] when all verify. A
     store.DeviceBoltStore takes the whole loop to the device in one dh_store_check_past call (cb then sees the first
     round of every window, not every round); only when the library refuses the file (too large for the device) or a
-    window (a stored record above 64 KiB) does the loop below run, over a BoltTrimmedStore of the same file."""
+    window (a stored record above 64 KiB) does the loop below run, over a BoltTrimmedStore (BoltUntrimmedStore for an
+    untrimmed store) of the same file. A record the store cannot decode is a Get error: the round is faulty."""
     from . import store as _store
     if isinstance(store, _store.DeviceBoltStore):
         try:
             return store.open().check_past(scheme, pubkey, up_to, cb=cb, window=window, seed=seed)
         except (_store.StoreTooLarge, _store.StrideTooLarge):
-            store = _store.BoltTrimmedStore(store.path, store.requires_previous)
+            untrimmed = store.untrimmed
+            if untrimmed is None:  # refused at open: the file decides, as open() would have
+                untrimmed = store.fmt == "untrimmed" or (store.fmt == "auto" and _store.looks_untrimmed(store.path))
+            store = (_store.BoltUntrimmedStore if untrimmed else _store.BoltTrimmedStore)(store.path, store.requires_previous)
     last = store.last()
     if last.round < up_to:
         up_to = last.round
@@ -100,7 +104,7 @@ def check_past_beacons(store, scheme, pubkey, up_to, cb=None, window=1 << 20, se
             cb(i, up_to)
         try:
             b = store.get(i)
-        except NoBeaconStored:
+        except (NoBeaconStored,) + _store.DECODE_ERRORS:  # a stored record its decoder rejects: Beacon.Unmarshal's error
             flush()  # keep the faulty list ascending
             faulty.append(i)
             if i >= up_to:

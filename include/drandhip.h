@@ -22,7 +22,8 @@
  * and adds the batch entry point the serial per-round loops need:
  *   chain/beacon/sync_manager.go:191-225 (CheckPastBeacons), client/verify.go:139-160, lp2p relays;
  * and the read path of the trimmed bolt store that loop runs over, parsed on the device from the store file:
- *   chain/boltdb/trimmed.go:87-107,156-193 (dh_store_*).
+ *   chain/boltdb/trimmed.go:87-107,156-193 (dh_store_*); and of the legacy untrimmed store, chain/boltdb/store.go:172-210
+ *   (dh_store_open_bolt_format, dh_store_beacons_device, dh_store_deferred).
  * INTEGRATION.md shows the cgo binding a drand maintainer would add.
  */
 #ifndef DRANDHIP_H
@@ -333,6 +334,60 @@ int dh_store_check_past(dh_store* store, int scheme, const uint8_t* pk, size_t p
                         uint64_t seed, uint64_t* faulty_out, size_t cap, size_t* n_faulty_out,
                         void (*cb)(uint64_t round, uint64_t up_to, void* arg), void* cb_arg);
 void dh_store_close(dh_store* store);
+
+/*
+ * Legacy untrimmed bbolt chain stores on the device: BoltStore of chain/boltdb/store.go:143-210, the
+ * format every store created before the trimmed one still has (store.go:82-110 keeps it). Same bucket and keys; the
+ * value is Beacon.Marshal() (chain/beacon.go:31-39), hexjson: {"PreviousSig":P,"Round":D,"Signature":S}. PreviousSig
+ * is the record's own field, so a missing round r - 1 does not fail round r, and Last() fails on an empty bucket only.
+ *
+ * The device decodes the CANONICAL form only: exactly those bytes, nothing before, between or after; P and S each null
+ * or a quoted even number (0 allowed) of characters 0-9a-f; D a decimal of 1-20 digits without a leading zero (0
+ * itself excepted) that fits 64 bits and equals the key. Stores written by drand are canonical throughout. Every other
+ * value (uppercase hex, odd digit count, whitespace, reordered or extra fields, Round != key, cut or trailing bytes)
+ * is DEFERRED: the device reports the record's key and decides nothing. The caller's host decoder decides it;
+ * drand_amd.store does so with its own restatement of Beacon.Unmarshal (beacon_from_hexjson), which is NOT pinned to
+ * nikkolasg/hexjson's decoder, so a verdict on a deferred record is that restatement's.
+ *
+ * dh_store_open_bolt_format: dh_store_open_bolt (= DH_STORE_TRIMMED) with the format named. DH_STORE_AUTO restates
+ * shouldUseTrimmedBolt on the first value of the bucket: canonical -> untrimmed; an empty bucket -> trimmed; a first
+ * byte '{' but not canonical -> DH_EINVAL (name the format); anything else -> trimmed.
+ */
+#define DH_STORE_TRIMMED 0
+#define DH_STORE_UNTRIMMED 1
+#define DH_STORE_AUTO 2
+#define DH_DEFERRED 1 /* success: the call skipped records that are not canonical hexjson (dh_store_deferred lists them) */
+int dh_store_open_bolt_format(const uint8_t* file, size_t len, int format, dh_store** out);
+/* out = {format (TRIMMED / UNTRIMMED, never AUTO), deferred round records, longest decoded Signature in bytes, longest
+ * decoded PreviousSig in bytes}; the last three are 0 for a trimmed store */
+int dh_store_format_stat(const dh_store* store, uint64_t out[4]);
+/*
+ * The beacons of rounds first..last of an untrimmed store (DH_EINVAL on a trimmed handle) as columns in device memory,
+ * in key order: d_rounds[i] = the key, d_deferred[i] = 1 for a deferred record (zero rows, zero lengths), else
+ * d_sig_lens[i] / d_prev_lens[i] = the decoded byte lengths and the hex-DECODED Signature / PreviousSig at
+ * d_sigs + i*sig_stride / d_prevs + i*prev_stride, copied whole and zero-padded when it fits its stride and left ALL
+ * ZERO when it does not (never a prefix). d_prevs and d_prev_lens are nullable together. Strides are multiples of 4,
+ * at most 1 MiB. The outputs feed dh_verify_batch_device directly (d_prevs / d_prev_lens for the chained scheme, NULL
+ * otherwise). d_missing, the capacities, DH_EINVAL with the sizes needed and hip_stream are those of
+ * dh_store_columns_device, which on an untrimmed handle keeps returning the raw stored values (the JSON text).
+ */
+int dh_store_beacons_device(dh_store* store, uint64_t first, uint64_t last, size_t sig_stride, size_t prev_stride,
+                            uint64_t* d_rounds, uint8_t* d_sigs, uint32_t* d_sig_lens, uint8_t* d_prevs, uint32_t* d_prev_lens,
+                            uint8_t* d_deferred, size_t cap_rows, size_t* n_rows_out, uint64_t* d_missing, size_t cap_missing,
+                            size_t* n_missing_out, void* hip_stream);
+/*
+ * dh_store_check_past on an untrimmed handle: the same loop bounds (Last(), the clamp, round < Len(), stop after the
+ * first round >= up_to), windows verified in place on the columns above with strides roundup4(max(dh_sig_len, the
+ * longest decoded value in the window's leaves)), a window above 64 KiB per row DH_EINVAL. A round is faulty when its
+ * record is missing, when its decoded Signature is not dh_sig_len bytes, or when dh_verify_batch_device rejects it
+ * with the PreviousSig it stores. Deferred records are skipped and the call then returns DH_DEFERRED instead of DH_OK;
+ * a deferred LAST record is DH_EINVAL (Last().Round is its Round field, which only the host decoder reads);
+ * DH_ENOBEACON only for an empty bucket.
+ *
+ * dh_store_deferred: the keys of the deferred records among rounds first..last, ascending (none on a trimmed handle);
+ * more than `cap`: DH_EINVAL with *n_out = the number needed.
+ */
+int dh_store_deferred(dh_store* store, uint64_t first, uint64_t last, uint64_t* out, size_t cap, size_t* n_out);
 
 /*
  * Synthetic-chain utilities (test fixtures and benchmark inputs; not part of the verification path):
