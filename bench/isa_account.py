@@ -4,7 +4,7 @@
 Static part, from the gfx950 code object of the built library (drand_amd/csrc/k_prep.o): the instruction mix of the
 out-of-line field-product bodies and of the kernel's loop bodies (the hot loops are the inlined Jacobian doublings of
 the subgroup test's two [|u|] runs), classified as
-  MAD64  v_mad_u64_u32                       (one partial product of the 28-bit schoolbook / Montgomery columns)
+  MAD64  v_mad_u64_u32 / v_mad_i64_i32       (one partial product of the 28-bit or signed 30-bit columns)
   V64    v_lshrrev_b64 / v_lshl_add_u64 ...  (the column carries)
   MUL32  v_mul_lo_u32                        (the Montgomery quotient digits)
   VALU   every other vector instruction       (masks, the limb-wise sums of the point formulas, moves, selects)
@@ -42,7 +42,7 @@ MANGLED = {"k_prep_sig<fp>": "_ZN2dh10k_prep_sigINS_2fpEEEvPKhmmPhPjS4_",
 
 def klass(ins):
     op = ins.split()[0]
-    if op.startswith("v_mad_u64_u32"):
+    if op.startswith(("v_mad_u64_u32", "v_mad_i64_i32")):
         return "MAD64"
     if op.startswith(("v_mul_lo_u32", "v_mul_hi_u32")):
         return "MUL32"

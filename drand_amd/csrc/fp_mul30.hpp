@@ -6,13 +6,16 @@
 // product-scanning reduction takes 13 x 13 + 13 x 13 = 338 MADs (v_mad_i64_i32) for a product and 91 + 169 = 260 for
 // a squaring. Unsigned 30-bit digits would not fit: 26 terms of 2^60 overflow the 64-bit column accumulator.
 // Centred, every term is <= 2^58 in magnitude, so a column of at most 13 + 13 terms plus the carry-in (< 2^34) stays
-// below 1.63 * 2^62 < 2^63 (tests/fp30_model.py restates the body on Python integers and asserts the bound at every
-// accumulation, the all-digits-at--2^29 operands included).
+// below 1.63 * 2^62 < 2^63, and the rounding bias of the output columns (2^29 + 2^59, see mont_body) fits on top
+// (tests/fp30_dep_model.py restates the body on Python integers in its accumulation order and asserts the bound at
+// every accumulation, the all-digits-at--2^29 operands included; tests/fp30_model.py is the body it replaced, column
+// sums from zero and one rounding add per column, which it must equal digit for digit).
 //
 // mont_mul(X, Y) = (X Y + m p) / 2^390 with m the centred quotient, |m| <= 2^389 (1 + 2^-30): for |X|, |Y| < 0.51 p
 // the result is within |X Y| / 2^390 + p / 2 + eps < 0.5006 p (p / 2^390 < 2^-9), so the chain needs no final
 // subtraction and its values never grow. The quotient columns shift exactly (acc + Mq[k] p[0] = 0 mod 2^30); the
-// output columns round to the nearest digit, R = sext30(acc), carry = (acc + 2^29) >> 30 (an arithmetic shift).
+// output columns round to the nearest digit, R = sext30(acc), carry = (acc + 2^29) >> 30 (an arithmetic shift; the
+// body adds the 2^29 of two columns at once).
 //
 // Entry (from): the 12 x 32-bit Montgomery value x 2^384 (< 2^384) is cut into 30-bit slices, which are recentred by a
 // carry pass BEFORE the conversion product (unsigned slices against a centred constant reach 13 (2^59 + 2^58)
@@ -69,47 +72,122 @@ DH_HD int32_t K_OUT(int i) {
 // the low 30 bits of v as a signed value in [-2^29, 2^29)
 DH_HD int32_t sext30(uint32_t v) { return (int32_t)(v << 2) >> 2; }
 
-// product-scanning Montgomery reduction over the column sums given by COL(k, acc); R may be X or Y (column k reads
-// digits >= k - 12 and writes digit k - 13)
-#define M30_BODY(COL)                                                                    \
-  int32_t Mq[N];                                                                         \
-  int64_t acc = 0;                                                                       \
-  _Pragma("unroll") for (int k = 0; k < N; k++) {                                        \
-    COL(k, acc);                                                                         \
-    _Pragma("unroll") for (int i = 0; i < k; i++) acc += (int64_t)Mq[i] * P(k - i);      \
-    Mq[k] = sext30((uint32_t)acc * N0);                                                  \
-    acc += (int64_t)Mq[k] * P(0);                                                        \
-    acc >>= 30;                                                                          \
-  }                                                                                      \
-  _Pragma("unroll") for (int k = N; k < 2 * N - 1; k++) {                                \
-    COL(k, acc);                                                                         \
-    _Pragma("unroll") for (int i = k - (N - 1); i < N; i++) acc += (int64_t)Mq[i] * P(k - i); \
-    R[k - N] = sext30((uint32_t)acc);                                                    \
-    acc = (acc + (1 << 29)) >> 30;                                                       \
-  }                                                                                      \
-  R[N - 1] = (int32_t)acc;
+// Pins the running column sums of the L lockstep operations on the device, after every MAD. Left to itself the
+// optimiser reassociates a column: it sums the products from zero and adds the carry of the column below afterwards,
+// one more 64-bit add per column (25 a body). A second use of every partial sum keeps the sum in source order, so the
+// carry is the addend of the column's first v_mad_i64_i32. One asm reads the sums of both operations, which also holds
+// the two MAD chains in lockstep (the scheduler otherwise runs twenty MADs of one chain, then twenty of the other).
+// The asm is empty and only reads. An asm that also wrote the sum ("+v") would pin as well, but the compiler then
+// guards every MAD that follows one with an s_nop (it must assume the asm's result needs a wait state), 242 a
+// squaring, and the body measured slower than the one it replaces (profiles/r14/microbench_fp30_dep.txt). A no-op on
+// the host.
+template <int L>
+DH_HD void pin(const int64_t acc[L]) {
+#if defined(__AMDGCN__)
+  if (L == 1)
+    asm volatile("" ::"v"(acc[0]));
+  else
+    asm volatile("" ::"v"(acc[0]), "v"(acc[L - 1]));
+#else
+  (void)acc;
+#endif
+}
+
+// Product-scanning Montgomery reduction of L independent operations in lockstep: every step of the body is written
+// once per operation, side by side, so a wave carries L independent MAD chains. The chains run L = 1. L = 2 (a pair
+// of chains walking one schedule, as the two square roots of the G1 hash could) is what bench/microbench_fp30.hip
+// measures beside it; it did not beat L = 1 there or in the hash kernel, so no kernel uses it.
+// SQ: the squaring, the off-diagonal products once against the doubled digits (in
+// [-2^30, 2^30)), 91 products instead of 169; Y is not read. R[l] may be X[l] or Y[l] (column k reads digits
+// >= k - 12 and writes digit k - 13).
+// The columns are dependent: column k + 1 starts on acc >> 30 of column k, with no separate carry add. The output
+// columns N .. 2N - 2 round in pairs. The first of a pair holds the true sum: its digit is sext30(acc), and
+// (acc + 2^29 + 2^59) >> 30 is the rounded carry plus 2^29. The second then holds true + 2^29: its digit is
+// sext30(acc ^ 2^29) and its plain shift is the rounded carry. That is one 64-bit add per two columns, and the bias
+// keeps |acc| < 1.63 * 2^62 + 2^59 (tests/fp30_dep_model.py restates this body and asserts it).
+constexpr int64_t BIAS = ((int64_t)1 << 29) + ((int64_t)1 << 59);
+// one MAD of every operation l, A and B being expressions in l
+#define M30_MAD(A, B)                                                             \
+  {                                                                               \
+    _Pragma("unroll") for (int l = 0; l < L; l++) acc[l] += (int64_t)(A) * (B);   \
+    pin<L>(acc);                                                                  \
+  }
+template <int L, bool SQ>
+DH_HD void mont_body(int32_t* const R[L], const int32_t* const X[L], const int32_t* const Y[L]) {
+  int32_t X2[L][N], Mq[L][N];
+  int64_t acc[L];
+#pragma unroll
+  for (int l = 0; l < L; l++) {
+    acc[l] = 0;
+#pragma unroll
+    for (int i = 0; i < N; i++) X2[l][i] = SQ ? X[l][i] + X[l][i] : 0;
+  }
+#pragma unroll
+  for (int k = 0; k < 2 * N - 1; k++) {
+    const int lo = k > N - 1 ? k - (N - 1) : 0, hi = k < N - 1 ? k : N - 1;
+    if (SQ) {
+#pragma unroll
+      for (int i = lo; 2 * i < k; i++) M30_MAD(X[l][i], X2[l][k - i])
+      if ((k & 1) == 0) M30_MAD(X[l][k / 2], X[l][k / 2])
+    } else {
+#pragma unroll
+      for (int i = lo; i <= hi; i++) M30_MAD(X[l][i], Y[l][k - i])
+    }
+    if (k < N) {  // a quotient column: shifts exactly
+#pragma unroll
+      for (int i = 0; i < k; i++) M30_MAD(Mq[l][i], P(k - i))
+#pragma unroll
+      for (int l = 0; l < L; l++) Mq[l][k] = sext30((uint32_t)acc[l] * N0);
+      M30_MAD(Mq[l][k], P(0))
+#pragma unroll
+      for (int l = 0; l < L; l++) acc[l] >>= 30;
+    } else {  // an output column
+#pragma unroll
+      for (int i = k - (N - 1); i < N; i++) M30_MAD(Mq[l][i], P(k - i))
+#pragma unroll
+      for (int l = 0; l < L; l++) {
+        if ((k - N) % 2 == 0) {
+          R[l][k - N] = sext30((uint32_t)acc[l]);
+          acc[l] = (acc[l] + BIAS) >> 30;
+        } else {
+          R[l][k - N] = sext30((uint32_t)acc[l] ^ (1u << 29));
+          acc[l] >>= 30;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int l = 0; l < L; l++) R[l][N - 1] = (int32_t)acc[l];
+}
+#undef M30_MAD
 
 // R = X Y / 2^390 (mod p), |R| <= |X Y| / 2^390 + p / 2
 DH_HD void mont_mul(int32_t R[N], const int32_t X[N], const int32_t Y[N]) {
-#define COLM(k, acc)                                                                                  \
-  _Pragma("unroll") for (int i = ((k) > N - 1 ? (k) - (N - 1) : 0); i <= ((k) < N - 1 ? (k) : N - 1); i++) \
-      acc += (int64_t)X[i] * Y[(k) - i];
-  M30_BODY(COLM)
-#undef COLM
+  int32_t* const r[1] = {R};
+  const int32_t* const x[1] = {X};
+  const int32_t* const y[1] = {Y};
+  mont_body<1, false>(r, x, y);
 }
 
-// R = X^2 / 2^390, the off-diagonal products once against the doubled digits (in [-2^30, 2^30)): 91 products
-// instead of 169
+// R = X^2 / 2^390
 DH_HD void mont_sqr(int32_t R[N], const int32_t X[N]) {
-  int32_t X2[N];
-#pragma unroll
-  for (int i = 0; i < N; i++) X2[i] = X[i] + X[i];
-#define COLS(k, acc)                                                                        \
-  _Pragma("unroll") for (int i = ((k) > N - 1 ? (k) - (N - 1) : 0); 2 * i < (k); i++)       \
-      acc += (int64_t)X[i] * X2[(k) - i];                                                   \
-  if (((k) & 1) == 0) acc += (int64_t)X[(k) / 2] * X[(k) / 2];
-  M30_BODY(COLS)
-#undef COLS
+  int32_t* const r[1] = {R};
+  const int32_t* const x[1] = {X};
+  mont_body<1, true>(r, x, x);
+}
+
+// (R0, R1) = (X0 Y0, X1 Y1) / 2^390 and (X0^2, X1^2) / 2^390, the two in lockstep
+DH_HD void mont_mul2(int32_t R0[N], int32_t R1[N], const int32_t X0[N], const int32_t X1[N], const int32_t Y0[N],
+                     const int32_t Y1[N]) {
+  int32_t* const r[2] = {R0, R1};
+  const int32_t* const x[2] = {X0, X1};
+  const int32_t* const y[2] = {Y0, Y1};
+  mont_body<2, false>(r, x, y);
+}
+DH_HD void mont_sqr2(int32_t R0[N], int32_t R1[N], const int32_t X0[N], const int32_t X1[N]) {
+  int32_t* const r[2] = {R0, R1};
+  const int32_t* const x[2] = {X0, X1};
+  mont_body<2, true>(r, x, x);
 }
 
 DH_HD el mul(const el& a, const el& b) {
