@@ -30,7 +30,8 @@ def main():
     rec = next(v for k, v in counts.items() if k.startswith("tbls-recover-n64-t33/"))
     rec_r = next((v for k, v in counts.items() if k.startswith("tbls-recover-n64-t33-random/")), None)
     units = {
-        "k_prep_sig<fp>": q["k_prep_sig<fp>"],
+        # 0 since r15: a large local G1 batch decodes inside the hash's launch, counted under k_prep_msg<fp>
+        "k_prep_sig<fp>": q.get("k_prep_sig<fp>", 0.0),
         "k_prep_msg<fp>": q["k_prep_msg<fp>"],
         "k_prep_sig<fp2>": u["k_prep_sig<fp2>"],
         "k_prep_msg<fp2>": u["k_prep_msg<fp2>"],
@@ -70,7 +71,10 @@ def main():
                          "(DESIGN 17): k_prep_msg<fp> 1123 -> 1074, k_prep_msg<fp2> 2155 -> 2099; the G2 figures are now "
                          "those of a 1,048,576-round batch with the batched G2 subgroup test of r09 (DESIGN 14: "
                          "k_prep_sig<fp2> = the decode-only kernel, 935 where the fused kernel counts 2138, plus "
-                         "k_sub_batch_level0<fp2>), which r09 had not carried into this file")
+                         "k_sub_batch_level0<fp2>), which r09 had not carried into this file. r15: a large local G1 batch "
+                         "runs its decode and its hash as one launch reported under k_prep_msg<fp> (DESIGN 20: the hash "
+                         "point's inversion rides the decode's square-root chain), so k_prep_sig<fp> is 0 and "
+                         "k_prep_msg<fp> is the sum, counted against 463 + 1074 = 1537 for the two kernels before")
     wm.pop("_doc_k_lagrange", None)
     with open(wm_path, "w") as f:
         json.dump(wm, f, indent=2)

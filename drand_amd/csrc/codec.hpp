@@ -74,6 +74,34 @@ DH_DEV uint8_t g1_decompress(aff<fp>& out, const uint8_t* b, bool subgroup) {
   return DEC_OK;
 }
 
+// g1_decompress (without the subgroup test) whose square-root chain also carries 1/c for the caller (h2c.hpp
+// fp_sqrt_ride), c != 0. Same statuses and the same point as g1_decompress. Every lane runs the chain, whatever its
+// encoding: one rejected before the root (compression bit clear, infinity flag, x >= p) rides on the stand-in a = 1
+// and keeps its status; a non-residue x^3 + 4 still yields 1/c. `out` is set only with DEC_OK.
+DH_DEV uint8_t g1_decompress_ride(aff<fp>& out, fp& inv_c, const uint8_t* b, const fp& c) {
+  uint32_t w[12];
+  be48_words(w, b, false);
+  const uint32_t flags = w[11] >> 29;
+  w[11] &= 0x1fffffffu;
+  uint32_t nz = flags & 1;
+#pragma unroll
+  for (int i = 0; i < 12; i++) nz |= w[i];
+  const uint8_t pre = !(flags & 4) ? DEC_BAD : (flags & 2) ? (nz ? DEC_BAD : DEC_INF) : int_lt_p(w) ? DEC_OK : DEC_BAD;
+  fp x;
+#pragma unroll
+  for (int i = 0; i < 12; i++) x.v[i] = pre == DEC_OK ? w[i] : 0;
+  x = fp_to_mont(x);
+  const fp rhs = fp_select(pre == DEC_OK, fp_add(fp_mul(fp_sqr(x), x), fp_c(cst::B1)), fp_one());
+  fp y;
+  const bool qr = fp_sqrt_ride(y, inv_c, rhs, c);
+  if (pre != DEC_OK) return pre;
+  if (!qr) return DEC_BAD;
+  if (fp_lex_gt_half(y) != (bool)(flags & 1)) y = fp_neg(y);
+  out.x = x;
+  out.y = y;
+  return DEC_OK;
+}
+
 // decode a 96-byte compressed G2 point (x.c1 || x.c0)
 DH_DEV uint8_t g2_decompress(aff<fp2>& out, const uint8_t* b, bool subgroup) {
   uint32_t w1[12], w0[12];

@@ -911,6 +911,17 @@ static int sub_backoff() {
   return v;
 }
 
+// A G1 batch that takes the batched subgroup test runs its decode and its hash as one per-round kernel, the hash
+// point's inversion riding on the decode's square-root chain (k_prep.hip round_g1_ride).
+// DRANDHIP_G1_RIDE=0 launches the two previous kernels (comparison runs).
+static bool g1_ride_on() {
+  static const bool v = [] {
+    const char* e = getenv("DRANDHIP_G1_RIDE");
+    return !(e && e[0] == '0');
+  }();
+  return v;
+}
+
 // MSM workspace of one bisection level (m entries in ngroups groups of geometry g, Jacobian width jw words); sub: also
 // the batched subgroup test's scratch (ws.sub)
 static int msm_workspace(worker* w, const dh::msm_geom& g, size_t m, size_t ngroups, size_t jw, dh::msm_ws& ws,
@@ -1014,18 +1025,27 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
       HIP_TRY(dh::launch_msm_sort(g0, w->entries.as<uint32_t>(), nullptr, nullptr, n, 1, w->scal.as<uint4>(), ws0, ts));
     }
     if (gate && gate->wait) HIP_TRY(hipStreamWaitEvent(st, gate->wait, 0));
-    HIP_TRY(T.run(g2 ? "k_prep_sig<fp2>" : "k_prep_sig<fp>", [&] {
-      return dh::launch_prep(g2, d_sigs, sig_stride, n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), d_rand, st,
-                             sub_batch);
-    }));
-    // hash points: of the beacon digests, or of the given 32-byte messages (VerifyRecovered); a chained record
-    // longer than its slot rejects its round (status)
-    HIP_TRY(w->h2c_tmp.ensure(dh::hash_tmp_bytes(g2, n)));
-    HIP_TRY(T.run(d_msgs32 ? (g2 ? "k_prep_msg32<fp2>" : "k_prep_msg32<fp>") : (g2 ? "k_prep_msg<fp2>" : "k_prep_msg<fp>"), [&] {
-      return dh::launch_hash(g2, d_rounds, d_prevs, prev_stride, d_prev_lens, d_msgs32, n,
-                             scheme == DH_SCHEME_CHAINED && d_prevs && !d_msgs32 ? 1 : 0, dst_id(scheme), w->status.as<uint8_t>(),
-                             w->q_pts.as<uint32_t>(), w->h2c_tmp.as<uint32_t>(), st);
-    }));
+    const int chained = scheme == DH_SCHEME_CHAINED && d_prevs && !d_msgs32 ? 1 : 0;
+    if (!g2 && sub_batch && g1_ride_on()) {
+      // decode and hash in one launch (reported under the hash's stage name)
+      HIP_TRY(T.run(d_msgs32 ? "k_prep_msg32<fp>" : "k_prep_msg<fp>", [&] {
+        return dh::launch_round_g1_ride(d_rounds, d_prevs, prev_stride, d_prev_lens, d_msgs32, n, chained, dst_id(scheme), d_sigs,
+                                        sig_stride, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), d_rand,
+                                        w->q_pts.as<uint32_t>(), st);
+      }));
+    } else {
+      HIP_TRY(T.run(g2 ? "k_prep_sig<fp2>" : "k_prep_sig<fp>", [&] {
+        return dh::launch_prep(g2, d_sigs, sig_stride, n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), d_rand, st,
+                               sub_batch);
+      }));
+      // hash points: of the beacon digests, or of the given 32-byte messages (VerifyRecovered); a chained record
+      // longer than its slot rejects its round (status)
+      HIP_TRY(w->h2c_tmp.ensure(dh::hash_tmp_bytes(g2, n)));
+      HIP_TRY(T.run(d_msgs32 ? (g2 ? "k_prep_msg32<fp2>" : "k_prep_msg32<fp>") : (g2 ? "k_prep_msg<fp2>" : "k_prep_msg<fp>"), [&] {
+        return dh::launch_hash(g2, d_rounds, d_prevs, prev_stride, d_prev_lens, d_msgs32, n, chained, dst_id(scheme),
+                               w->status.as<uint8_t>(), w->q_pts.as<uint32_t>(), w->h2c_tmp.as<uint32_t>(), st);
+      }));
+    }
     if (!presorted) {
       HIP_TRY(hipMemcpyAsync(d_seed, seedw, 32, hipMemcpyHostToDevice, st));
       HIP_TRY(dh::launch_scalars(d_seed, n, w->status.as<uint8_t>(), w->scal.as<uint4>(), parts, st));
@@ -2756,6 +2776,44 @@ int dh_hash_to_curve(int group, const uint8_t* msgs, const uint32_t* msg_off, si
                                  w->key_raw.as<uint8_t>(), (uint32_t)dst_len, w->h2c_tmp.as<uint8_t>(), stride,
                                  w->out_rand.as<uint8_t>(), st));
   HIP_TRY(hipMemcpyAsync(out, w->out_rand.p, n * outlen, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DH_OK;
+}
+
+// 48 big-endian bytes < p
+static bool fp_bytes_canonical(const uint8_t* b) {
+  static const uint8_t P[48] = {0x1a, 0x01, 0x11, 0xea, 0x39, 0x7f, 0xe6, 0x9a, 0x4b, 0x1b, 0xa7, 0xb6, 0x43, 0x4b, 0xac, 0xd7,
+                                0x64, 0x77, 0x4b, 0x84, 0xf3, 0x85, 0x12, 0xbf, 0x67, 0x30, 0xd2, 0xa0, 0xf6, 0xb0, 0xf6, 0x24,
+                                0x1e, 0xab, 0xff, 0xfe, 0xb1, 0x53, 0xff, 0xff, 0xb9, 0xfe, 0xff, 0xff, 0xff, 0xff, 0xaa, 0xab};
+  return memcmp(b, P, 48) < 0;
+}
+
+int dh_g1_round_prep_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uint8_t* status_out, uint8_t* sig_out,
+                           uint8_t* hash_out) {
+  if (!us || !sigs || !status_out || !sig_out || !hash_out) return fail(DH_EINVAL, "null argument");
+  if (n == 0) return DH_OK;
+  for (size_t i = 0; i < 2 * n; i++)
+    if (!fp_bytes_canonical(us + 48 * i)) return fail(DH_EINVAL, "field element %zu is not below p", i);
+  lease L;
+  if (L.rc) return L.rc;
+  worker* w = L.w;
+  int rc = set_device_and_stream(w);
+  if (rc) return rc;
+  hipStream_t st = w->stream;
+  HIP_TRY(w->in_prevs.ensure(n * 96));
+  HIP_TRY(w->in_sigs.ensure(n * 48));
+  HIP_TRY(w->status.ensure(n));
+  HIP_TRY(w->sig_aff.ensure(n * JAC_WORDS_G1 * 2 / 3 * 4));
+  HIP_TRY(w->q_pts.ensure(n * JAC_WORDS_G1 * 4));
+  HIP_TRY(w->out_rand.ensure(n * 192));
+  HIP_TRY(hipMemcpyAsync(w->in_prevs.p, us, n * 96, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w->in_sigs.p, sigs, n * 48, hipMemcpyHostToDevice, st));
+  uint8_t* out = w->out_rand.as<uint8_t>();
+  HIP_TRY(dh::launch_round_g1_ride_debug(w->in_prevs.as<uint8_t>(), w->in_sigs.as<uint8_t>(), n, w->status.as<uint8_t>(),
+                                         w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(), out, out + n * 96, st));
+  HIP_TRY(hipMemcpyAsync(status_out, w->status.p, n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(sig_out, out, n * 96, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(hash_out, out + n * 96, n * 96, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return DH_OK;
 }

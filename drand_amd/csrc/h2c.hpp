@@ -159,6 +159,81 @@ DH_DEV jac<fp> h2c_g1_map(const fp& u0, const fp& u1) {
   return jac_add(iso11_jac(p0), iso11_jac(p1));
 }
 
+// ---------------------------------------------------------------- G1: the affine sum on an inverse that rides a chain
+// p = 3 mod 4, so for t != 0 and w = t^((p-3)/4): w^2 = chi(t) / t with chi the quadratic character. A square-root
+// chain that some other code needs anyway (the signature decode's, on a = x^3 + 4) is run on t = a c^2 instead, for
+// any c != 0 (chi(t) = chi(a)):
+//   y = w a c          y^2 = chi(a) a: a root of a exactly when a is a square (the caller fixes its sign)
+//   1/c = chi(a) w^2 a c
+// Five products around the chain (a c, a c^2, y, w^2, w^2 a c) and the check y^2 == a that a root needs anyway.
+// Branch-free; c == 0 gives y = 0, inv_c = 0 and false (callers pass c != 0). a != 0 for a curve's right-hand side
+// x^3 + 4 (-4 is not a cube mod p) and for the stand-in a = 1.
+DH_DEV bool fp_sqrt_ride(fp& y, fp& inv_c, const fp& a, const fp& c) {
+  const fp ac = fp_mul(a, c);
+  const fp w = fp_pow_sched(fp_mul(ac, c), cst::SCHED_SR1_C1, cst::SCHED_SR1_C1_LEN);
+  y = fp_mul(w, ac);
+  const fp ic = fp_mul(fp_sqr(w), ac);
+  const bool qr = fp_eq(fp_sqr(y), a);
+  inv_c = fp_select(qr, ic, fp_neg(ic));
+  return qr;
+}
+
+// The sum of the two SSWU points P_i = (xn_i / xd_i, y_i) on E1', affine, on ONE inverse. With A = xn0 xd1,
+// B = xn1 xd0, D = xd0 xd1 (x0 = A / D, x1 = B / D), N = B - A and c = N D:
+//   1/D = N / c,  lambda = (y1 - y0) D / N = (y1 - y0) D^2 / c,
+//   x3 = lambda^2 - (A + B) / D,  y3 = lambda (A / D - x3) - y0.
+// g1_sum_pre (6 products) leaves the five values the tail needs across the chain that carries 1/c, and c;
+// g1_sum_post (6 products) builds (x3, y3) from them and 1/c. c == 0 exactly when N == 0 (xd_i != 0: swu_jac), the
+// two points sharing x: g1_sum_pre then returns false and the caller takes h2c_g1_map's exceptional order.
+struct g1_sum_mid {
+  fp n, s, a, dyd2, y0;  // N, A + B, A, (y1 - y0) D^2, y0
+};
+DH_DEV bool g1_sum_pre(g1_sum_mid& m, fp& c, const swu_out<fp>& p0, const swu_out<fp>& p1) {
+  m.a = fp_mul(p0.xn, p1.xd);
+  const fp b = fp_mul(p1.xn, p0.xd);
+  const fp d = fp_mul(p0.xd, p1.xd);
+  m.n = fp_sub(b, m.a);
+  m.s = fp_add(b, m.a);
+  c = fp_mul(m.n, d);
+  m.dyd2 = fp_mul(fp_sub(p1.y, p0.y), fp_sqr(d));
+  m.y0 = p0.y;
+  return !fp_is_zero(m.n);
+}
+DH_DEV aff<fp> g1_sum_post(const g1_sum_mid& m, const fp& inv_c) {
+  const fp inv_d = fp_mul(m.n, inv_c);
+  const fp lam = fp_mul(m.dyd2, inv_c);
+  aff<fp> r;
+  r.x = fp_sub(fp_sqr(lam), fp_mul(m.s, inv_d));
+  r.y = fp_sub(fp_mul(lam, fp_sub(fp_mul(m.a, inv_d), r.x)), m.y0);
+  return r;
+}
+
+// iso11_jac on an affine point of E1' (Z = 1, so D = 1): three plain Horner evaluations on the same lazily reduced
+// 28-bit form and the same tables, acc = acc * X + c_{d-j}. Value bounds in units of p: a product's result is < 2, a
+// table constant < 1, so a Horner accumulator is < 3 and every product here is at most 3 x 2; X' = x_num < 3 and
+// Z' = h < 3 go to f28_to_fp, which accepts < 4. The Jacobian image is (X', Y', Z') = (x_num(x), y y_num(x), h(x)):
+// the same point as iso11_jac's. Z' = 0 exactly when h(x) = 0 (the point is in the isogeny's kernel); an affine input
+// is never the identity. 31 products: 11 + 15 Horner steps, 4 for the monic h, y y_num; two conversion products in
+// and three out.
+DH_DEV jac<fp> iso11_aff(const aff<fp>& p) {
+  using namespace cst;
+  const f28 X = f28_from_fp(p.x);                                      // < 2
+  f28 xn = f28_c(ISO11_XNUM_28[ISO11_XNUM_LEN - 1]);                    // < 1
+  f28 yn = f28_c(ISO11_YNUM_28[ISO11_YNUM_LEN - 1]);                    // < 1
+  f28 h = X;                                                            // the leading coefficient is 1
+#pragma unroll 1
+  for (int j = 1; j < ISO11_YNUM_LEN; j++) {
+    yn = f28_add(f28_mul(yn, X), f28_c(ISO11_YNUM_28[ISO11_YNUM_LEN - 1 - j]));  // < 3
+    if (j < ISO11_XNUM_LEN) xn = f28_add(f28_mul(xn, X), f28_c(ISO11_XNUM_28[ISO11_XNUM_LEN - 1 - j]));
+    if (j < ISO11_H_LEN) h = f28_add(j > 1 ? f28_mul(h, X) : h, f28_c(ISO11_H_28[ISO11_H_LEN - 1 - j]));
+  }
+  jac<fp> r;
+  r.x = f28_to_fp(xn);
+  r.y = f28_to_fp(f28_mul(f28_from_fp(p.y), yn));
+  r.z = f28_to_fp(h);
+  return r;
+}
+
 DH_DEV jac<fp> h2c_g1_noclear(const sha_h& digest, int dst_id) {
   uint32_t b[4][8];
   xmd32<4>(b, digest, dst_id);

@@ -7,6 +7,8 @@
 //                  on the level-0 sigma buckets, k_msm.hip launch_sub_batch; a large local G2 batch
 //                  likewise: k_dec_sig_g2 without k_sub_sig_g2)
 //   k_prep_msg     DigestBeacon + hash_to_curve without cofactor clearing               [A2, A3, A4b]
+//                  (a large local G1 batch: k_round_g1_ride does this and the decode above on one lane, the hash
+//                  point's inversion riding the decode's square-root chain)
 //   k_scalars      128-bit random-linear-combination scalars r_i = SHA-256(seed || i)   [batching, new]
 //   MSM (grouped Pippenger, shared sort for both point sets):
 //     k_msm_hist -> scan -> k_msm_scatter -> k_msm_bucket28<S>, k_msm_bucket28<Q> -> k_msm_segsum28 -> k_msm_tree28
@@ -254,6 +256,93 @@ __global__ __launch_bounds__(256, occ<fp>::W) void k_prep_msg_g1(const uint64_t*
   st_jac_aos<fp>(q_out, i, h2c_g1_noclear(d, dst_id));
 }
 
+// G1, a large local batch (launch_round_g1_ride): the round's hash and its signature decode on one lane, so that the
+// decode's square-root chain carries the inverse that makes the sum of the two SSWU points affine (h2c.hpp
+// fp_sqrt_ride, g1_sum_pre / g1_sum_post) and the 11-isogeny three plain Horner evaluations (iso11_aff). Outputs are
+// dec_sig_g1's (status, the affine sigma, randomness) and k_prep_msg_g1's (a Jacobian representative of the same hash
+// point: k_msm_prep28 makes both affine). msg_ok: false rejects the round as message_of does. When the two SSWU points
+// share x (never for hashed inputs) the chain rides on c = 1 and the lane takes h2c_g1_map in a divergent branch, on
+// the u0, u1 it parked in its q_out slot (24 of the slot's 36 words, as the G2 passes park theirs): with the branch
+// recomputing them from the message the kernel's scratch frame was 1,088 B a lane against 688.
+DH_DEV void round_g1_ride(const fp& u0, const fp& u1, bool msg_ok, const uint8_t* __restrict__ s, size_t i,
+                          uint8_t* __restrict__ status, uint32_t* __restrict__ sig_aff, uint8_t* __restrict__ rand_out,
+                          uint32_t* __restrict__ q_out) {
+  st_f<fp>(q_out + 36 * i, u0);
+  st_f<fp>(q_out + 36 * i + 12, u1);
+  g1_sum_mid m;
+  fp c;
+  const bool distinct = g1_sum_pre(m, c, sswu_g1(u0), sswu_g1(u1));
+  c = fp_select(distinct, c, fp_one());
+  fp inv_c;
+  {
+    aff<fp> a;
+    uint8_t st = g1_decompress_ride(a, inv_c, s, c);
+    if (rand_out) st_digest(rand_out + 32 * i, sha256_aligned<48>(s));
+    if (st != DEC_OK) {
+      a.x = fp{};
+      a.y = fp{};
+      st = DEC_BAD;  // infinity signatures are rejected like kilic's engine + kyber's verify
+    }
+    status[i] = msg_ok ? st : (uint8_t)DEC_BAD;
+    st_aff_aos<fp>(sig_aff, i, a);
+  }
+  if (distinct) {
+    st_jac_aos<fp>(q_out, i, iso11_aff(g1_sum_post(m, inv_c)));
+  } else {
+    fp v0, v1;
+    ld_f<fp>(v0, q_out + 36 * i);
+    ld_f<fp>(v1, q_out + 36 * i + 12);
+    st_jac_aos<fp>(q_out, i, h2c_g1_map(v0, v1));
+  }
+}
+
+__global__ __launch_bounds__(256, occ<fp>::W) void k_round_g1_ride(const uint64_t* __restrict__ rounds, const uint8_t* __restrict__ prevs,
+                                                              size_t prev_stride, const uint32_t* __restrict__ prev_lens,
+                                                              const uint8_t* __restrict__ msgs32, size_t n, int chained, int dst_id,
+                                                              const uint8_t* __restrict__ sigs, size_t stride,
+                                                              uint8_t* __restrict__ status, uint32_t* __restrict__ sig_aff,
+                                                              uint8_t* __restrict__ rand_out, uint32_t* __restrict__ q_out) {
+  size_t i = gtid();
+  if (i >= n) return;
+  sha_h d;
+  bool msg_ok = true;
+  if (msgs32) d = message_of(nullptr, nullptr, 0, nullptr, msgs32, 0, i, nullptr);
+  else msg_ok = beacon_digest(d, rounds, prevs, prev_stride, prev_lens, chained, i);
+  uint32_t b[4][8];
+  xmd32<4>(b, d, dst_id);
+  round_g1_ride(fp_from_be512(b[0], b[1]), fp_from_be512(b[2], b[3]), msg_ok, sigs + i * stride, i, status, sig_aff, rand_out,
+                q_out);
+}
+
+// the test entry's kernels (dh_g1_round_prep_debug): round_g1_ride from given u0, u1 (2 x 48 big-endian bytes a round,
+// canonical), then sigma and the hash point as canonical affine x || y (2 x 48 big-endian bytes each; the identity,
+// and a rejected signature, as zeros)
+__global__ __launch_bounds__(256, occ<fp>::W) void k_round_g1_ride_debug(const uint8_t* __restrict__ u, size_t n,
+                                                                    const uint8_t* __restrict__ sigs, size_t stride,
+                                                                    uint8_t* __restrict__ status, uint32_t* __restrict__ sig_aff,
+                                                                    uint32_t* __restrict__ q_out) {
+  size_t i = gtid();
+  if (i >= n) return;
+  fp u0, u1;
+  be48_words(u0.v, u + 96 * i, false);
+  be48_words(u1.v, u + 96 * i + 48, false);
+  round_g1_ride(fp_to_mont(u0), fp_to_mont(u1), true, sigs + i * stride, i, status, sig_aff, nullptr, q_out);
+}
+__global__ __launch_bounds__(64) void k_round_g1_debug_out(size_t n, const uint32_t* __restrict__ sig_aff,
+                                                           const uint32_t* __restrict__ q_pts, uint8_t* __restrict__ sig_out,
+                                                           uint8_t* __restrict__ q_out) {
+  size_t i = gtid();
+  if (i >= n) return;
+  const aff<fp> s = ld_aff_aos<fp>(sig_aff, i);
+  st_be48(sig_out + 96 * i, fp_from_mont(s.x));
+  st_be48(sig_out + 96 * i + 48, fp_from_mont(s.y));
+  const jac<fp> q = ld_jac_aos<fp>(q_pts, i);
+  aff<fp> a{fp{}, fp{}};
+  if (!jac_is_inf(q)) a = jac_to_aff(q);
+  st_be48(q_out + 96 * i, fp_from_mont(a.x));
+  st_be48(q_out + 96 * i + 48, fp_from_mont(a.y));
+}
+
 // G2 in three passes. The G2 map keeps more Fp2 values live than one lane's 256 VGPRs hold (fused, the kernel
 // needed 19.3 KB of scratch per lane, and 8 such 1M-round dispatches in flight failed to launch), so the state
 // between the passes goes through HBM: u0, u1 (192 B per round) and the two SSWU points on E2' (576 B per
@@ -487,6 +576,24 @@ hipError_t launch_hash(int sig_g2, const uint64_t* rounds, const uint8_t* prevs,
   hipLaunchKernelGGL(k_h2f_g2, dim3(nblk(n, 256)), dim3(256), 0, st, rounds, prevs, prev_stride, prev_lens, msgs32, n, chained,
                      dst_id, status, q_out);
   return hash_g2_map(n, q_out, tmp, st);
+}
+
+hipError_t launch_round_g1_ride(const uint64_t* rounds, const uint8_t* prevs, size_t prev_stride, const uint32_t* prev_lens,
+                                const uint8_t* msgs32, size_t n, int chained, int dst_id, const uint8_t* sigs, size_t stride,
+                                uint8_t* status, uint32_t* sig_aff, uint8_t* rand_out, uint32_t* q_out, hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(k_round_g1_ride, dim3(nblk(n, 256)), dim3(256), 0, st, rounds, prevs, prev_stride, prev_lens, msgs32, n,
+                     chained, dst_id, sigs, stride, status, sig_aff, rand_out, q_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_round_g1_ride_debug(const uint8_t* u, const uint8_t* sigs, size_t n, uint8_t* status, uint32_t* sig_aff,
+                                      uint32_t* q_pts, uint8_t* sig_out, uint8_t* q_out, hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(k_round_g1_ride_debug, dim3(nblk(n, 256)), dim3(256), 0, st, u, n, sigs, (size_t)48, status, sig_aff, q_pts);
+  hipLaunchKernelGGL(k_round_g1_debug_out, dim3(nblk(n, 64)), dim3(64), 0, st, n, (const uint32_t*)sig_aff,
+                     (const uint32_t*)q_pts, sig_out, q_out);
+  return hipGetLastError();
 }
 
 hipError_t launch_hash_var(int sig_g2, const uint8_t* msgs, const uint32_t* msg_off, size_t n, int dst_id, uint32_t* q_out,

@@ -90,6 +90,16 @@ size_t hash_tmp_bytes(int sig_g2, size_t n);
 hipError_t launch_hash(int sig_g2, const uint64_t* rounds, const uint8_t* prevs, size_t prev_stride, const uint32_t* prev_lens,
                        const uint8_t* msgs32, size_t n, int chained, int dst_id, uint8_t* status, uint32_t* q_out, uint32_t* tmp,
                        hipStream_t st);
+// G1 signatures, a large local batch: launch_prep(defer_sub = true) and launch_hash in one launch, one round per lane,
+// the hash point's affine sum on an inverse carried by the signature's square-root chain (k_prep.hip round_g1_ride).
+// Same status, sig_aff and rand_out; q_out holds another Jacobian representative of the same hash points.
+hipError_t launch_round_g1_ride(const uint64_t* rounds, const uint8_t* prevs, size_t prev_stride, const uint32_t* prev_lens,
+                                const uint8_t* msgs32, size_t n, int chained, int dst_id, const uint8_t* sigs, size_t stride,
+                                uint8_t* status, uint32_t* sig_aff, uint8_t* rand_out, uint32_t* q_out, hipStream_t st);
+// the same per-round code from given u0 || u1 (96 canonical big-endian bytes a round) and 48-byte signatures; sig_out
+// and q_out: canonical affine x || y (96 bytes a round), zeros for the identity; sig_aff / q_pts: n x 24 / 36 words
+hipError_t launch_round_g1_ride_debug(const uint8_t* u, const uint8_t* sigs, size_t n, uint8_t* status, uint32_t* sig_aff,
+                                      uint32_t* q_pts, uint8_t* sig_out, uint8_t* q_out, hipStream_t st);
 // the same hash points for messages of any length, message i = msgs[msg_off[i] .. msg_off[i + 1]) (sign.Scheme.Verify
 // in batch: xmd_any, sha256.hpp); tmp: hash_tmp_bytes(sig_g2, n)
 hipError_t launch_hash_var(int sig_g2, const uint8_t* msgs, const uint32_t* msg_off, size_t n, int dst_id, uint32_t* q_out,

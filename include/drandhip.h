@@ -410,6 +410,17 @@ int dh_hash_to_curve(int group, const uint8_t* msgs, const uint32_t* msg_off, si
                      uint8_t* out);
 
 /*
+ * Test entry: the per-round kernel of a large local G1-signature batch (decode and hash on one lane, the hash
+ * point's inversion carried by the signature's square-root chain) from hash_to_field's outputs on. us: n pairs
+ * u0 || u1 as canonical 48-byte big-endian field elements (each < p); sigs: n 48-byte compressed signatures.
+ * status_out: n bytes (1 = decoded; no subgroup test); sig_out: n x 96 bytes, sigma as canonical affine x || y (zeros
+ * when rejected); hash_out: n x 96 bytes, map_to_curve(u0) + map_to_curve(u1) before cofactor clearing as canonical
+ * affine x || y, zeros for the identity.
+ */
+int dh_g1_round_prep_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uint8_t* status_out, uint8_t* sig_out,
+                           uint8_t* hash_out);
+
+/*
  * Live kernel timing: when enabled, every device stage of the verification path is bracketed by HIP
  * events on the stream it is launched on; dh_profile_read writes a JSON object
  * {"stage": {"count": c, "total_ms": t}, ...} into buf (returns the full length). dh_profile resets.
