@@ -548,7 +548,7 @@ dh::msm_geom geom_for(size_t gsize, int parts = 1) {
 // alone fill the chip, and geom_for's fixed 8-bucket segments had doubled the reduction's additions there (a
 // 129-bucket row: 16 segments = 256 + ~150 segoff additions against 256 + 7 for 2).
 static void fit_segments(dh::msm_geom& g, size_t ngroups, size_t nsets) {
-  const size_t rows = std::max<size_t>(1, nsets * ngroups * (size_t)g.nwin);
+  const size_t rows = std::max<size_t>(1, nsets * ngroups * (size_t)dh::msm_rows(g));
   const size_t want = ((size_t)1 << 18) / rows + 1;
   size_t nseg = std::max<size_t>(1, std::min<size_t>({want, (size_t)g.nseg}));
   if (nseg > 512) nseg &= ~(size_t)511;  // rows of more than 64 lanes of 8 segments fill whole waves (k_msm_rowtree28)
@@ -922,17 +922,30 @@ static bool g1_ride_on() {
   return v;
 }
 
+// Such a batch also leaves the hash's 11-isogeny to the MSM: the per-round kernel stores the affine sum
+// of the two SSWU points on E1' straight into the MSM's arrays (no k_msm_prep28 at level 0), level 0 runs with the
+// scalar halves in window rows of their own (msm_geom split) and maps the hash set's eight row sums to E1. A batch
+// that level 0 does not end falls back to the isogeny per round and the usual arrays (points beside their images) before level 1.
+// DRANDHIP_G1_ISO_LATE=0 keeps the isogeny in the per-round kernel (comparison runs).
+static bool g1_iso_late_on() {
+  static const bool v = [] {
+    const char* e = getenv("DRANDHIP_G1_ISO_LATE");
+    return !(e && e[0] == '0');
+  }();
+  return v;
+}
+
 // MSM workspace of one bisection level (m entries in ngroups groups of geometry g, Jacobian width jw words); sub: also
 // the batched subgroup test's scratch (ws.sub)
 static int msm_workspace(worker* w, const dh::msm_geom& g, size_t m, size_t ngroups, size_t jw, dh::msm_ws& ws,
                          bool sub = false, bool g2 = false) {
-  const size_t nk = ngroups * g.nwin * (size_t)g.nbuck;
+  const size_t nk = ngroups * dh::msm_rows(g) * (size_t)g.nbuck;
   HIP_TRY(w->cnt.ensure(nk * 4));
   HIP_TRY(w->off.ensure((nk + 1) * 4));
   HIP_TRY(w->scan_tmp.ensure(((nk + 4095) / 4096 + 1) * 4));
   HIP_TRY(w->list.ensure(dh::msm_entries(g, m) * 4));
   HIP_TRY(w->buckets.ensure(2 * nk * jw * 4));
-  const size_t segs_bytes = 2 * ngroups * g.nwin * g.nseg * jw * 4;
+  const size_t segs_bytes = 2 * ngroups * dh::msm_rows(g) * g.nseg * jw * 4;
   HIP_TRY(w->segs.ensure(2 * segs_bytes));  // segment sums, then (MSM28) the segments' running sums
   HIP_TRY(w->outA.ensure(ngroups * jw * 4));
   HIP_TRY(w->outB.ensure(ngroups * jw * 4));
@@ -989,6 +1002,8 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
   const bool sub_batch = sub_eligible && w->sub_fused_left == 0;
   if (sub_eligible && w->sub_fused_left > 0) w->sub_fused_left--;  // after a dense fallback (sub_backoff)
   const int parts = g2 && !sub_batch ? 4 : 2;
+  const bool g1_ride = !g2 && sub_batch && g1_ride_on();
+  const bool iso_late = g1_ride && g1_iso_late_on();  // level 0 on split rows, the hash set on E1'
   // sorted-list entries keep a sign bit and address parts * n points (the endomorphism images follow the n points)
   if (n >= ((size_t)1 << 31) / parts) return fail(DH_EINVAL, "batch too large");
   dh::msm_geom g0{};
@@ -1020,13 +1035,23 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
       HIP_TRY(dh::launch_iota(w->entries.as<uint32_t>(), n, ts));
       g0 = geom_for(n, parts);
       g0.half_stride = (uint32_t)n;
+      g0.split = iso_late ? 1 : 0;
       rc = msm_workspace(w, g0, n, 1, wsw, ws0, sub_batch, g2);
       if (rc) return rc;
       HIP_TRY(dh::launch_msm_sort(g0, w->entries.as<uint32_t>(), nullptr, nullptr, n, 1, w->scal.as<uint4>(), ws0, ts));
     }
     if (gate && gate->wait) HIP_TRY(hipStreamWaitEvent(st, gate->wait, 0));
     const int chained = scheme == DH_SCHEME_CHAINED && d_prevs && !d_msgs32 ? 1 : 0;
-    if (!g2 && sub_batch && g1_ride_on()) {
+    HIP_TRY(w->s28.ensure(parts * n * (g2 ? 64 : 32) * 4));
+    HIP_TRY(w->q28.ensure(parts * n * (g2 ? 64 : 32) * 4));
+    if (iso_late) {
+      // decode and hash in one launch, sigma and the E1' hash point straight into the MSM's arrays
+      HIP_TRY(T.run(d_msgs32 ? "k_prep_msg32<fp>" : "k_prep_msg<fp>", [&] {
+        return dh::launch_round_g1_ride_late(d_rounds, d_prevs, prev_stride, d_prev_lens, d_msgs32, n, chained, dst_id(scheme),
+                                             d_sigs, sig_stride, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), d_rand,
+                                             w->q_pts.as<uint32_t>(), w->s28.as<uint32_t>(), w->q28.as<uint32_t>(), st);
+      }));
+    } else if (g1_ride) {
       // decode and hash in one launch (reported under the hash's stage name)
       HIP_TRY(T.run(d_msgs32 ? "k_prep_msg32<fp>" : "k_prep_msg<fp>", [&] {
         return dh::launch_round_g1_ride(d_rounds, d_prevs, prev_stride, d_prev_lens, d_msgs32, n, chained, dst_id(scheme), d_sigs,
@@ -1050,12 +1075,12 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
       HIP_TRY(hipMemcpyAsync(d_seed, seedw, 32, hipMemcpyHostToDevice, st));
       HIP_TRY(dh::launch_scalars(d_seed, n, w->status.as<uint8_t>(), w->scal.as<uint4>(), parts, st));
     }
-    HIP_TRY(w->s28.ensure(parts * n * (g2 ? 64 : 32) * 4));
-    HIP_TRY(w->q28.ensure(parts * n * (g2 ? 64 : 32) * 4));
-    HIP_TRY(T.run(g2 ? "k_msm_prep28<fp2>" : "k_msm_prep28<fp>", [&] {
-      return dh::launch_msm_prep28(g2, n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(),
-                                   w->s28.as<uint32_t>(), w->q28.as<uint32_t>(), st, 3, parts);
-    }));
+    if (!iso_late) {
+      HIP_TRY(T.run(g2 ? "k_msm_prep28<fp2>" : "k_msm_prep28<fp>", [&] {
+        return dh::launch_msm_prep28(g2, n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(),
+                                     w->s28.as<uint32_t>(), w->q28.as<uint32_t>(), st, 3, parts);
+      }));
+    }
     HIP_TRY(hipMemsetAsync(d_verdict, 0, n, st));
     if (gate) {
       HIP_TRY(hipEventRecord(gate->done, st));
@@ -1103,6 +1128,7 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
     gsize = std::min(gsize, m);
     dh::msm_geom g = geom_for(gsize, parts);
     g.half_stride = (uint32_t)n;
+    g.split = level == 0 && iso_late ? 1 : 0;
     const size_t ngroups = (m + gsize - 1) / gsize;
     fit_segments(g, ngroups, 2);
     const bool pre = level == 0 && presorted;
@@ -1169,6 +1195,16 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
       HIP_TRY(hipMemcpyAsync(&nbad, (uint8_t*)w->sub_pass.p + 4, 4, hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
       if ((double)nbad * 2000 > (double)n) w->sub_fused_left = sub_backoff();
+    }
+    if (level == 0 && iso_late && nfail32) {
+      // level 0 did not end the batch: the isogeny per round after all, then the usual arrays (both sets with their
+      // images), so that the bisection and the leaves see what they see without the deferral
+      HIP_TRY(T.run("k_msm_prep28<fp>", [&] {
+        hipError_t e = dh::launch_iso_late_fallback(n, w->status.as<uint8_t>(), w->q28.as<uint32_t>(), w->q_pts.as<uint32_t>(), st);
+        if (e != hipSuccess) return e;
+        return dh::launch_msm_prep28(0, n, w->status.as<uint8_t>(), w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(),
+                                     w->s28.as<uint32_t>(), w->q28.as<uint32_t>(), st, 3, parts);
+      }));
     }
     level++;
     const size_t nfail = nfail32;
@@ -2811,6 +2847,39 @@ int dh_g1_round_prep_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uin
   uint8_t* out = w->out_rand.as<uint8_t>();
   HIP_TRY(dh::launch_round_g1_ride_debug(w->in_prevs.as<uint8_t>(), w->in_sigs.as<uint8_t>(), n, w->status.as<uint8_t>(),
                                          w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(), out, out + n * 96, st));
+  HIP_TRY(hipMemcpyAsync(status_out, w->status.p, n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(sig_out, out, n * 96, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(hash_out, out + n * 96, n * 96, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DH_OK;
+}
+
+int dh_g1_round_prep_late_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uint8_t* status_out, uint8_t* sig_out,
+                                uint8_t* hash_out) {
+  if (!us || !sigs || !status_out || !sig_out || !hash_out) return fail(DH_EINVAL, "null argument");
+  if (n == 0) return DH_OK;
+  for (size_t i = 0; i < 2 * n; i++)
+    if (!fp_bytes_canonical(us + 48 * i)) return fail(DH_EINVAL, "field element %zu is not below p", i);
+  lease L;
+  if (L.rc) return L.rc;
+  worker* w = L.w;
+  int rc = set_device_and_stream(w);
+  if (rc) return rc;
+  hipStream_t st = w->stream;
+  HIP_TRY(w->in_prevs.ensure(n * 96));
+  HIP_TRY(w->in_sigs.ensure(n * 48));
+  HIP_TRY(w->status.ensure(n));
+  HIP_TRY(w->sig_aff.ensure(n * JAC_WORDS_G1 * 2 / 3 * 4));
+  HIP_TRY(w->q_pts.ensure(n * JAC_WORDS_G1 * 4));
+  HIP_TRY(w->s28.ensure(n * 32 * 4));
+  HIP_TRY(w->q28.ensure(n * 32 * 4));
+  HIP_TRY(w->out_rand.ensure(n * 192));
+  HIP_TRY(hipMemcpyAsync(w->in_prevs.p, us, n * 96, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w->in_sigs.p, sigs, n * 48, hipMemcpyHostToDevice, st));
+  uint8_t* out = w->out_rand.as<uint8_t>();
+  HIP_TRY(dh::launch_round_g1_ride_late_debug(w->in_prevs.as<uint8_t>(), w->in_sigs.as<uint8_t>(), n, w->status.as<uint8_t>(),
+                                              w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(), w->s28.as<uint32_t>(),
+                                              w->q28.as<uint32_t>(), out, out + n * 96, st));
   HIP_TRY(hipMemcpyAsync(status_out, w->status.p, n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(sig_out, out, n * 96, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(hash_out, out + n * 96, n * 96, hipMemcpyDeviceToHost, st));

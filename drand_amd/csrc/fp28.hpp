@@ -270,7 +270,45 @@ DH_DEV j28 j28_inf() {
   return r;
 }
 
+// The same doubling on a curve y^2 = x^3 + a x + b with a != 0 (E1', the 11-isogenous curve the G1 hash's SSWU map
+// lands on): E = 3 X^2 + a Z^4, three more products (Z^2, Z^4, a Z^4 < 2), so E < 8 and E (D + 26p - X3) is 8 x 38.
+// In (X, Y, Z) <= (48, 50, 50) with Y Z <= 2500 -> out (26, 18, 4). a28: a in the 28-bit Montgomery form, < 1.
+DH_DEV j28 j28_dbl_a(const j28& p, const f28& a28) {
+  const f28 a = f28_sqr(p.x);                                          // < 2
+  const f28 b = f28_sqr(p.y);                                          // < 2
+  const f28 c = f28_sqr(b);                                            // < 2
+  const f28 t = f28_sqr(f28_add(p.x, b));                              // (X + B)^2, X + B < 50
+  const f28 d = f28_lin3<8>(t, 2, a, -2, c, -2);                       // D = 2 (T + 4p - A - C) < 12
+  const f28 az4 = f28_mul(a28, f28_sqr(f28_sqr(p.z)));                 // a Z^4 < 2
+  const f28 e = f28_lin<0>(a, 3, az4, 1);                              // E = 3A + a Z^4 < 8
+  const f28 f = f28_sqr(e);                                            // < 2
+  j28 r;
+  r.x = f28_lin<24>(f, 1, d, -2);                                      // F + 24p - 2D < 26
+  const f28 m = f28_mul(e, f28_sub<26>(d, r.x));                       // 8 x 38 -> < 2
+  r.y = f28_lin<16>(m, 1, c, -8);                                      // M + 16p - 8C < 18
+  r.z = f28_scale(f28_mul(p.y, p.z), 2);                               // < 4
+  r.inf = p.inf;
+  return r;
+}
+// E1' : y^2 = x^3 + A' x + B' (RFC 9380 8.8.1): A' R' mod p in 28-bit limbs
+DH_DEV f28 f28_e1p_a() {
+  const uint32_t k[14] = {0x5effb65u, 0x7b0e9afu, 0x2c3688cu, 0x2e2fbe8u, 0xf093be0u, 0x4e56b8eu, 0x51e099cu,
+                          0x22aa2e7u, 0xbb7ea2bu, 0x50194edu, 0xaee9f0bu, 0x4130e5du, 0x3ac15b2u, 0x0019762u};
+  f28 r;
+#pragma unroll
+  for (int i = 0; i < 14; i++) r.l[i] = k[i];
+  return r;
+}
+// the doubling the exact additions below fall back on when both operands are equal: the curve's (a = 0: E1; E1P: E1')
+struct j28_on_e1 {
+  DH_DEV static j28 dbl(const j28& p) { return j28_dbl(p); }
+};
+struct j28_on_e1p {
+  DH_DEV static j28 dbl(const j28& p) { return j28_dbl_a(p, f28_e1p_a()); }
+};
+
 // madd-2007-bl, q affine (x, y < 2), full special cases as curve.hpp jac_add_aff. In (26, 18, 6) -> out (8, 6, 6)
+template <class CURVE = j28_on_e1>
 DH_DEV j28 j28_madd(const j28& p, const f28& qx, const f28& qy) {
   if (p.inf) return j28{qx, qy, f28_one(), false};
   const f28 z1z1 = f28_sqr(p.z);                                       // < 2
@@ -279,7 +317,7 @@ DH_DEV j28 j28_madd(const j28& p, const f28& qx, const f28& qy) {
   const f28 h = f28_sub<26>(u2, p.x);                                  // < 28
   const f28 rr = f28_sub<18>(s2, p.y);                                 // < 20
   if (f28_zero(h)) {
-    if (f28_zero(rr)) return j28_dbl(p);
+    if (f28_zero(rr)) return CURVE::dbl(p);
     return j28_inf();
   }
   const f28 hh = f28_sqr(h);                                           // 28^2 -> < 2
@@ -297,6 +335,7 @@ DH_DEV j28 j28_madd(const j28& p, const f28& qx, const f28& qy) {
 }
 
 // add-2007-bl, full special cases as curve.hpp jac_add. In (26, 18, 6) x (26, 18, 6) -> out (8, 6, 2)
+template <class CURVE = j28_on_e1>
 DH_DEV j28 j28_add(const j28& p, const j28& q) {
   if (p.inf) return q;
   if (q.inf) return p;
@@ -307,7 +346,7 @@ DH_DEV j28 j28_add(const j28& p, const j28& q) {
   const f28 h = f28_sub<2>(u2, u1);                                    // < 4
   const f28 rr = f28_sub<2>(s2, s1);                                   // < 4
   if (f28_zero(h)) {
-    if (f28_zero(rr)) return j28_dbl(p);
+    if (f28_zero(rr)) return CURVE::dbl(p);
     return j28_inf();
   }
   const f28 i = f28_sqr(f28_scale(h, 2));                              // < 2

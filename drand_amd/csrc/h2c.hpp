@@ -208,6 +208,22 @@ DH_DEV aff<fp> g1_sum_post(const g1_sum_mid& m, const fp& inv_c) {
   return r;
 }
 
+// 2 P on E1' for an SSWU output P = (xn / xd, y), affine, on one inversion (the exceptional branch of the form that
+// leaves the isogeny to the batch): with c = 2 y xd^2, lambda = (3 xn^2 + A' xd^2) / c and 1 / xd = 2 y xd / c,
+//   x3 = lambda^2 - 2 x,  y3 = lambda (x - x3) - y.
+// E1'(Fp) has odd order (it is isogenous to E1), so y != 0, and xd != 0 (swu_jac): c != 0.
+DH_DEV aff<fp> e1p_dbl_aff(const swu_out<fp>& p) {
+  const fp xd2 = fp_sqr(p.xd), y2 = fp_dbl(p.y);
+  const fp ic = fp_inv(fp_mul(y2, xd2));
+  const fp xn2 = fp_sqr(p.xn);
+  const fp lam = fp_mul(fp_add(fp_add(fp_dbl(xn2), xn2), fp_mul(fp_c(cst::SSWU1_A), xd2)), ic);
+  const fp x = fp_mul(p.xn, fp_mul(fp_mul(y2, p.xd), ic));
+  aff<fp> r;
+  r.x = fp_sub(fp_sqr(lam), fp_dbl(x));
+  r.y = fp_sub(fp_mul(lam, fp_sub(x, r.x)), p.y);
+  return r;
+}
+
 // iso11_jac on an affine point of E1' (Z = 1, so D = 1): three plain Horner evaluations on the same lazily reduced
 // 28-bit form and the same tables, acc = acc * X + c_{d-j}. Value bounds in units of p: a product's result is < 2, a
 // table constant < 1, so a Horner accumulator is < 3 and every product here is at most 3 x 2; X' = x_num < 3 and

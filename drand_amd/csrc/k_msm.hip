@@ -1,4 +1,5 @@
 // Grouped Pippenger MSM for the random-linear-combination batch check (gfx950).
+#include <type_traits>
 #include "kcommon.hpp"
 
 namespace dh {
@@ -43,6 +44,12 @@ DH_DEV uint4 half_scalar(const uint4& s, uint32_t h, const msm_geom& g) {
   if (g.halves == 4) return make_uint4(h == 0 ? s.x : h == 1 ? s.y : h == 2 ? s.z : s.w, 0, 0, 0);
   return h ? make_uint4(s.z, s.w, 0, 0) : make_uint4(s.x, s.y, 0, 0);
 }
+// the key row of window w of half h in group gi, and the half's point index: the halves share their group's nwin rows
+// and the images sit half_stride points on, or (g.split) each half has its own nwin rows and the point itself
+DH_DEV size_t key_row(const msm_geom& g, size_t gi, uint32_t h, int w) {
+  return gi * msm_rows(g) + (g.split ? h * (uint32_t)g.nwin : 0u) + (uint32_t)w;
+}
+DH_DEV uint32_t half_point(const msm_geom& g, uint32_t idx0, uint32_t h) { return g.split ? idx0 : idx0 + h * g.half_stride; }
 // the round of a point index: the endomorphism images follow the n points (parts of half_stride = nround points)
 DH_DEV uint32_t round_of(uint32_t idx, uint32_t nround) { return idx < nround ? idx : idx % nround; }
 
@@ -58,7 +65,7 @@ __global__ void k_msm_hist(const uint32_t* __restrict__ pidx, const uint32_t* __
     uint32_t carry = 0;
     for (int w = 0; w < g.nwin; w++) {
       const int32_t d = signed_digit(sh, w, g, carry);
-      if (d) atomicAdd(&cnt[(gi * g.nwin + w) * g.nbuck + (uint32_t)(d < 0 ? -d : d)], 1u);
+      if (d) atomicAdd(&cnt[key_row(g, gi, h, w) * g.nbuck + (uint32_t)(d < 0 ? -d : d)], 1u);
     }
   }
 }
@@ -73,12 +80,12 @@ __global__ void k_msm_scatter(const uint32_t* __restrict__ pidx, const uint32_t*
   const size_t gi = entry_group(grp, e, g.gsize);
   for (uint32_t h = 0; h < g.halves; h++) {
     const uint4 sh = half_scalar(s, h, g);
-    const uint32_t idx = idx0 + h * g.half_stride;  // endo(P) sits half_stride points after P
+    const uint32_t idx = half_point(g, idx0, h);  // endo(P) sits half_stride points after P
     uint32_t carry = 0;
     for (int w = 0; w < g.nwin; w++) {
       const int32_t d = signed_digit(sh, w, g, carry);
       if (d) {
-        uint32_t pos = atomicAdd(&cursor[(gi * g.nwin + w) * g.nbuck + (uint32_t)(d < 0 ? -d : d)], 1u);
+        uint32_t pos = atomicAdd(&cursor[key_row(g, gi, h, w) * g.nbuck + (uint32_t)(d < 0 ? -d : d)], 1u);
         list[pos] = d < 0 ? (idx | NEG_BIT) : idx;
       }
     }
@@ -101,7 +108,7 @@ __global__ __launch_bounds__(SORT_T) void k_msm_sort_lds(const uint32_t* __restr
                                                          uint32_t* __restrict__ gcnt, uint32_t* __restrict__ list) {
   extern __shared__ uint32_t h[];  // slab counters (dynamic: slab x 4 bytes)
   const size_t e0 = (size_t)blockIdx.x * tile, e1 = min(m, e0 + tile);
-  const size_t rowkeys = (size_t)g.nwin * g.nbuck;
+  const size_t rowkeys = (size_t)msm_rows(g) * g.nbuck;
   // the tile's key span: its groups' rows (entries of a group are consecutive without grp), else every key
   const size_t kb = grp ? 0 : (e0 / g.gsize) * rowkeys, ke = grp ? nk : min(nk, ((e1 - 1) / g.gsize + 1) * rowkeys);
   const size_t K0 = kb + (size_t)blockIdx.y * slab;
@@ -109,19 +116,29 @@ __global__ __launch_bounds__(SORT_T) void k_msm_sort_lds(const uint32_t* __restr
   const uint32_t ns = (uint32_t)min((size_t)slab, ke - K0);
   for (uint32_t k = threadIdx.x; k < ns; k += SORT_T) h[k] = 0;
   __syncthreads();
+  // split rows: a slab inside one group's rows holds keys of the halves [h_lo, h_hi] only (at c = 16 a slab is about
+  // one row), so the other half's digits are not recoded for it
+  uint32_t h_lo = 0, h_hi = g.halves - 1;
+  if (g.split) {
+    const size_t r0 = K0 / g.nbuck, r1 = (K0 + ns - 1) / g.nbuck, R = msm_rows(g);
+    if (r0 / R == r1 / R) {
+      h_lo = (uint32_t)(r0 % R) / (uint32_t)g.nwin;
+      h_hi = (uint32_t)(r1 % R) / (uint32_t)g.nwin;
+    }
+  }
   // f(key in the slab, point index | sign) for every digit of the tile's entries
   auto each = [&](auto&& f) {
     for (size_t e = e0 + threadIdx.x; e < e1; e += SORT_T) {
       const uint32_t idx0 = pidx[e];
       const uint4 s = scal[sidx ? sidx[e] : idx0];
       const size_t gi = entry_group(grp, e, g.gsize);
-      for (uint32_t hh = 0; hh < g.halves; hh++) {
+      for (uint32_t hh = h_lo; hh <= h_hi; hh++) {
         const uint4 sh = half_scalar(s, hh, g);
-        const uint32_t idx = idx0 + hh * g.half_stride;
+        const uint32_t idx = half_point(g, idx0, hh);
         uint32_t carry = 0;
         for (int w = 0; w < g.nwin; w++) {
           const int32_t d = signed_digit(sh, w, g, carry);
-          const size_t key = (gi * g.nwin + w) * g.nbuck + (uint32_t)(d < 0 ? -d : d);
+          const size_t key = key_row(g, gi, hh, w) * g.nbuck + (uint32_t)(d < 0 ? -d : d);
           if (d && key - K0 < ns) f((uint32_t)(key - K0), d < 0 ? (idx | NEG_BIT) : idx);
         }
       }
@@ -294,7 +311,8 @@ hipError_t launch_scan(const uint32_t* cnt, size_t nk, uint32_t* off, uint32_t* 
 
 hipError_t launch_msm_sort(const msm_geom& g, const uint32_t* pidx, const uint32_t* sidx, const uint32_t* grp, size_t m,
                            size_t ngroups, const uint4* scal, msm_ws& ws, hipStream_t st) {
-  size_t nk = ngroups * g.nwin * (size_t)g.nbuck;
+  if (g.split && g.halves != 2) return hipErrorInvalidValue;
+  size_t nk = ngroups * msm_rows(g) * (size_t)g.nbuck;
   ws.max_entries = msm_entries(g, m);
   hipError_t e = hipMemsetAsync(ws.cnt, 0, nk * sizeof(uint32_t), st);
   if (e != hipSuccess) return e;
@@ -317,7 +335,9 @@ hipError_t launch_msm_sort(const msm_geom& g, const uint32_t* pidx, const uint32
       const long d = v ? atol(v) : 0;
       return (size_t)(d >= 1 && d <= 256 ? d : 8);
     }();
-    const size_t digits = (size_t)g.halves * g.nwin, rowkeys = (size_t)g.nwin * g.nbuck;
+    // digits an entry sends to one group's rows that can share a slab: with split rows a slab of at most one window row
+    // at c = 16 sees one half's, so the tiles are twice as long for the same density (and as many workgroups)
+    const size_t digits = (size_t)(g.split ? 1 : g.halves) * g.nwin, rowkeys = (size_t)msm_rows(g) * g.nbuck;
     // DRANDHIP_SORT_SLAB: the LDS slab in keys (smaller slabs let the workgroups share a CU with the kernels beside them)
     static const size_t slab_max = [] {
       const char* v = getenv("DRANDHIP_SORT_SLAB");
@@ -359,26 +379,6 @@ hipError_t launch_msm_sort(const msm_geom& g, const uint32_t* pidx, const uint32
 // Stored Fp elements take 16 words (14 limbs + 2 pad: four 16-byte loads), a Jacobian point 3 elements, infinity
 // stored as Z = 0 (all limbs zero: a finite point's Z is never 0 mod p). The window sums leave in the 12 x 32-bit
 // Montgomery Jacobian form the pairing checks read.
-constexpr int W28 = 16;
-DH_DEV f28 ld28(const uint32_t* p) {
-  const uint4* q = (const uint4*)p;
-  f28 a;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const uint4 t = q[i];
-    a.l[4 * i] = t.x;
-    a.l[4 * i + 1] = t.y;
-    if (4 * i + 2 < 14) a.l[4 * i + 2] = t.z;
-    if (4 * i + 3 < 14) a.l[4 * i + 3] = t.w;
-  }
-  return a;
-}
-DH_DEV void st28(uint32_t* p, const f28& a) {
-  uint4* q = (uint4*)p;
-#pragma unroll
-  for (int i = 0; i < 4; i++)
-    q[i] = make_uint4(a.l[4 * i], a.l[4 * i + 1], 4 * i + 2 < 14 ? a.l[4 * i + 2] : 0u, 4 * i + 3 < 14 ? a.l[4 * i + 3] : 0u);
-}
 DH_DEV void ld28(f28& a, const uint32_t* p) { a = ld28(p); }
 DH_DEV void st28(uint32_t* p, const f28& a, int) { st28(p, a); }
 DH_DEV void ld28(f228& a, const uint32_t* p) {
@@ -445,6 +445,25 @@ struct c28_g1 {
   DH_DEV static E endo_x(const E& x);
   DH_DEV static E endo_y(const E& y) { return y; }
 };
+// the same on E1', the curve the G1 hash's SSWU sums lie on before the 11-isogeny (the hash set of a split-row level 0,
+// DESIGN §21): the additions never use the curve's a, so only the doublings differ: those the exact additions fall back
+// on when both operands are equal, and the segment offsets' (k_msm_segoff28)
+struct c28_g1p : c28_g1 {
+  DH_DEV static P madd(const P& a, const E& x, const E& y) { return j28_madd<j28_on_e1p>(a, x, y); }
+  DH_DEV static P add(const P& a, const P& b) { return j28_add<j28_on_e1p>(a, b); }
+  template <bool EXACT>
+  DH_DEV static P add_mem(const P& a, const uint32_t* q) {
+    j28 b;
+    b.x = ld28(q);
+    b.y = ld28(q + W28);
+    b.z = ld28(q + 2 * W28);
+    b.inf = z_all_zero(b.z);
+    return EXACT ? j28_add<j28_on_e1p>(a, b) : j28_add_fast(a, b);
+  }
+  template <bool EXACT>
+  DH_DEV static P addx(const P& a, const P& b) { return EXACT ? j28_add<j28_on_e1p>(a, b) : j28_add_fast(a, b); }
+  DH_DEV static P dbl(const P& a) { return j28_on_e1p::dbl(a); }
+};
 struct c28_g2 {
   static constexpr int OCC = 1;  // 512 registers: the G2 mixed addition's values fit VGPRs + AGPRs, no scratch
   static constexpr bool IS_G2 = true;
@@ -487,6 +506,26 @@ struct c28_g2 {
   DH_DEV static E psi2_x(const E& x) { return f2_red({f28_mul(x.c0, f28_c(PSI2_X28)), f28_mul(x.c1, f28_c(PSI2_X28))}); }
   DH_DEV static E psi2_y(const E& y) { return f2_red({f28_mul(y.c0, f28_c(PSI2_Y28)), f28_mul(y.c1, f28_c(PSI2_Y28))}); }
 };
+
+// The reduction kernels take both point sets' rows in one launch: rows from prime_from on (the hash set's, in a
+// split-row level 0; NO_PRIME otherwise) are on the curve prime_of<C>. f(curve) runs on the row's curve.
+template <class C>
+struct prime_of {
+  using T = C;
+};
+template <>
+struct prime_of<c28_g1> {
+  using T = c28_g1p;
+};
+constexpr size_t NO_PRIME = ~(size_t)0;
+template <class C, class FN>
+DH_DEV typename C::P on_curve(bool prime, FN&& f) {
+  using CP = typename prime_of<C>::T;
+  if constexpr (!std::is_same<C, CP>::value) {
+    if (prime) return f(CP{});
+  }
+  return f(C{});
+}
 
 template <class C>
 DH_DEV typename C::P ldj28(const uint32_t* base, size_t i) {
@@ -844,7 +883,7 @@ __attribute__((noinline)) DH_DEV typename C::P add_lds_exact(const uint32_t* buf
 // sum of lanes [l, l + span). Every thread of the workgroup calls it (barriers); buf: lds_words<C>() x blockDim words.
 // The inputs are exact (stored points), so a poisoned sum is recomputed with the exact formulas on the spot.
 template <class C>
-DH_DEV typename C::P wave_tree(typename C::P acc, uint32_t* buf, uint32_t span) {
+DH_DEV typename C::P wave_tree(typename C::P acc, uint32_t* buf, uint32_t span, bool prime = false) {
   const int nthr = blockDim.x, i = threadIdx.x, lane = i & 63;
 #pragma unroll 1
   for (uint32_t step = 1; step < span; step <<= 1) {
@@ -856,8 +895,12 @@ DH_DEV typename C::P wave_tree(typename C::P acc, uint32_t* buf, uint32_t span) 
       typename C::P s = add_lds<C, false>(acc, buf, nthr, i + (int)step);
       if (C::poisoned(s)) {
         if constexpr (C::IS_G2) s = add_lds_exact<C>(buf, nthr, i, i + (int)step);
-        else s = add_lds<C, true>(lds_get_pt<C>(buf, nthr, i), buf, nthr, i + (int)step);  // G1: a call would cost
-      }                                                                                        // the second wave/SIMD
+        else  // G1: a call would cost the second wave/SIMD
+          s = on_curve<C>(prime, [&](auto k) {
+            using K = decltype(k);
+            return add_lds<K, true>(lds_get_pt<K>(buf, nthr, i), buf, nthr, i + (int)step);
+          });
+      }
       acc = s;
     }
     __syncthreads();
@@ -868,7 +911,7 @@ DH_DEV typename C::P wave_tree(typename C::P acc, uint32_t* buf, uint32_t span) 
 template <class C>
 __global__ __launch_bounds__(256, C::OCC) void k_msm_segsum28(const uint32_t* __restrict__ buckets, const uint32_t* __restrict__ off,
                                                               msm_geom g, size_t ngw, size_t rows_per_set, uint32_t* __restrict__ segs,
-                                                              uint32_t* __restrict__ runs) {
+                                                              uint32_t* __restrict__ runs, size_t prime_from) {
   const size_t t = gtid();
   if (t >= ngw * g.nseg) return;
   const size_t gw = t / g.nseg;
@@ -879,7 +922,11 @@ __global__ __launch_bounds__(256, C::OCC) void k_msm_segsum28(const uint32_t* __
   const size_t krow = (gw % rows_per_set) * g.nbuck, brow = gw * g.nbuck;
   typename C::P run, tot;
   seg_run<C, false>(buckets, off, krow, brow, a, last, run, tot);
-  if (C::poisoned(run) || C::poisoned(tot)) seg_run<C, true>(buckets, off, krow, brow, a, last, run, tot);
+  if (C::poisoned(run) || C::poisoned(tot))
+    on_curve<C>(gw >= prime_from, [&](auto k) {
+      seg_run<decltype(k), true>(buckets, off, krow, brow, a, last, run, tot);
+      return tot;
+    });
   stj28<C>(segs, t, tot);
   stj28<C>(runs, t, run);
 }
@@ -898,7 +945,7 @@ DH_DEV typename C::P seg_off(const uint32_t* __restrict__ run, uint32_t k, const
 }
 template <class C>
 __global__ __launch_bounds__(256, C::OCC) void k_msm_segoff28(msm_geom g, size_t ngw, uint32_t* __restrict__ segs,
-                                                              const uint32_t* __restrict__ runs) {
+                                                              const uint32_t* __restrict__ runs, size_t prime_from) {
   const size_t t = gtid();
   if (t >= ngw * g.nseg) return;
   const uint32_t k = (t % g.nseg) * g.seglen;  // a - 1
@@ -906,8 +953,13 @@ __global__ __launch_bounds__(256, C::OCC) void k_msm_segoff28(msm_geom g, size_t
   const uint32_t* run = runs + (size_t)3 * C::EW * t;
   if (ldj28<C>(runs, t).inf) return;  // run at infinity: the segment's value is tot as stored
   uint32_t* tot = segs + (size_t)3 * C::EW * t;
-  typename C::P r = seg_off<C, false>(run, k, tot);
-  if (C::poisoned(r)) r = seg_off<C, true>(run, k, tot);
+  // the doublings are the row's curve's (whole waves take one side: a row holds many segments)
+  const typename C::P r = on_curve<C>(t / g.nseg >= prime_from, [&](auto c) {
+    using K = decltype(c);
+    typename C::P v = seg_off<K, false>(run, k, tot);
+    if (K::poisoned(v)) v = seg_off<K, true>(run, k, tot);
+    return v;
+  });
   stj28<C>(segs, t, r);
 }
 
@@ -922,40 +974,44 @@ __global__ __launch_bounds__(256, C::OCC) void k_msm_segoff28(msm_geom g, size_t
 // 2 windows of 2,048 segments, gpurun_out r05w): the pure wave tree was 8.2 ms against 4.4.
 template <class C>
 __global__ __launch_bounds__(256, C::OCC) void k_msm_rowtree28(const uint32_t* __restrict__ segs, uint32_t nseg, uint32_t G,
-                                                               size_t ngw, uint32_t lpr, uint32_t span, uint32_t* __restrict__ out) {
+                                                               size_t ngw, uint32_t lpr, uint32_t span, uint32_t* __restrict__ out,
+                                                               size_t prime_from) {
   __shared__ uint32_t buf[lds_words<C>() * 256];
   const size_t t = gtid();
   typename C::P acc = C::inf();
+  const bool prime = t / lpr >= prime_from;
   if (t < ngw * lpr) {
     const size_t row = t / lpr;
     const uint32_t s0 = (uint32_t)(t % lpr) * G;
     const uint32_t* p = segs + (size_t)3 * C::EW * (row * nseg + s0);
     const uint32_t cnt = s0 >= nseg ? 0 : min(G, nseg - s0);
     acc = run_mem<C, false>(p, cnt);
-    if (C::poisoned(acc)) acc = run_mem<C, true>(p, cnt);
+    if (C::poisoned(acc)) acc = on_curve<C>(prime, [&](auto k) { return run_mem<decltype(k), true>(p, cnt); });
   }
-  acc = wave_tree<C>(acc, buf, span);
+  acc = wave_tree<C>(acc, buf, span, prime);
   if (t < ngw * lpr && (t & (span - 1)) == 0) stj28<C>(out, t / span, acc);
 }
 template <class C>
 __global__ __launch_bounds__(64) void k_msm_rowred28(const uint32_t* __restrict__ parts_in, uint32_t parts, uint32_t span,
-                                                     uint32_t* __restrict__ rowsum) {
+                                                     uint32_t* __restrict__ rowsum, size_t prime_from) {
   __shared__ uint32_t buf[lds_words<C>() * 64];
   const size_t row = blockIdx.x;
+  const bool prime = row >= prime_from;
   typename C::P acc = run_mem<C, false>(parts_in, row * parts, parts);
-  if (C::poisoned(acc)) acc = run_mem<C, true>(parts_in, row * parts, parts);
-  acc = wave_tree<C>(acc, buf, span);
+  if (C::poisoned(acc))
+    acc = on_curve<C>(prime, [&](auto k) { return run_mem<decltype(k), true>(parts_in, row * parts, parts); });
+  acc = wave_tree<C>(acc, buf, span, prime);
   if (threadIdx.x == 0) stj28<C>(rowsum, row, acc);
 }
 
 template <class C, bool EXACT>
-DH_DEV typename C::P horner28(const uint32_t* __restrict__ rowsum, const msm_geom& g, size_t t) {
-  typename C::P acc = ldj28<C>(rowsum, t * g.nwin + g.nwin - 1);
+DH_DEV typename C::P horner28(const uint32_t* __restrict__ rowsum, const msm_geom& g, size_t row0) {
+  typename C::P acc = ldj28<C>(rowsum, row0 + g.nwin - 1);
 #pragma unroll 1
   for (int w = g.nwin - 2; w >= 0; w--) {
 #pragma unroll 1
     for (int k = 0; k < g.c; k++) acc = C::dbl(acc);
-    acc = C::template add_mem<EXACT>(acc, rowsum + (size_t)3 * C::EW * (t * g.nwin + w));
+    acc = C::template add_mem<EXACT>(acc, rowsum + (size_t)3 * C::EW * (row0 + w));
   }
   return acc;
 }
@@ -966,8 +1022,8 @@ __global__ __launch_bounds__(64) void k_msm_windows28(const uint32_t* __restrict
                                                       uint32_t* __restrict__ out) {
   const size_t t = gtid();
   if (t >= ngroups) return;
-  typename C::P acc = horner28<C, false>(rowsum, g, t);
-  if (C::poisoned(acc)) acc = horner28<C, true>(rowsum, g, t);
+  typename C::P acc = horner28<C, false>(rowsum, g, t * g.nwin);
+  if (C::poisoned(acc)) acc = horner28<C, true>(rowsum, g, t * g.nwin);
   jac<typename C::F> r = jac_inf<typename C::F>();
   if (!acc.inf) {
     r.x = C::out(acc.x);
@@ -975,6 +1031,47 @@ __global__ __launch_bounds__(64) void k_msm_windows28(const uint32_t* __restrict
     r.z = C::out(acc.z);
   }
   st_jac_aos<typename C::F>(out, t, r);
+}
+
+// Split rows (G1). The hash set's row sums are on E1': the 11-isogeny takes each to E1 first, in place, one
+// lane per row sum (iso11_jac; a sum in the isogeny's kernel becomes the identity), so that the Horner doublings below
+// are E1's for both sets.
+__global__ __launch_bounds__(64) void k_msm_iso_rows28(uint32_t* __restrict__ rowsum, size_t first, size_t nrows) {
+  const size_t t = gtid();
+  if (t >= nrows) return;
+  const j28 p = ldj28<c28_g1>(rowsum, first + t);
+  if (p.inf) return;
+  const jac<fp> q = iso11_jac(jac<fp>{f28_to_fp(p.x), f28_to_fp(p.y), f28_to_fp(p.z)});
+  j28 r = j28_inf();
+  if (!fp_is_zero(q.z)) r = j28{f28_from_fp(q.x), f28_from_fp(q.y), f28_from_fp(q.z), false};
+  stj28<c28_g1>(rowsum, first + t, r);
+}
+// per (set, group) two lanes: A = Horner over the a-halves' rows, B = Horner over the b-halves' rows, then
+// out = A + phi(B) with phi(X, Y, Z) = (beta X, Y, Z), by the exact addition (A = phi(B), or either the identity)
+template <class C>
+__global__ __launch_bounds__(64) void k_msm_windows28_split(const uint32_t* __restrict__ rowsum, msm_geom g, size_t nsg,
+                                                            uint32_t* __restrict__ out) {
+  __shared__ uint32_t buf[lds_words<C>() * 64];
+  const size_t t = gtid(), u = t >> 1;
+  const bool half = t & 1;
+  typename C::P acc = C::inf();
+  if (u < nsg) {
+    const size_t row0 = u * msm_rows(g) + (half ? g.nwin : 0);
+    acc = horner28<C, false>(rowsum, g, row0);
+    if (C::poisoned(acc)) acc = horner28<C, true>(rowsum, g, row0);
+    if (half && !acc.inf) acc.x = C::endo_x(acc.x);  // X < 26 by a constant < 1
+  }
+  if (half) lds_put_pt<C>(buf, 64, threadIdx.x, acc);
+  __syncthreads();
+  if (half || u >= nsg) return;
+  acc = C::add(acc, lds_get_pt<C>(buf, 64, threadIdx.x + 1));
+  jac<typename C::F> r = jac_inf<typename C::F>();
+  if (!acc.inf) {
+    r.x = C::out(acc.x);
+    r.y = C::out(acc.y);
+    r.z = C::out(acc.z);
+  }
+  st_jac_aos<typename C::F>(out, u, r);
 }
 
 hipError_t launch_msm_prep28(int sig_g2, size_t n, uint8_t* status, const uint32_t* sig_aff, const uint32_t* q_pts,
@@ -1006,7 +1103,9 @@ static unsigned few_waves_block(size_t nthreads) { return nthreads <= 256 * 64 ?
 template <class C>
 static hipError_t msm28(const msm_geom& g, size_t ngroups, const uint32_t* S, const uint32_t* Q, msm_ws& ws, hipStream_t st,
                         const uint8_t* skip, int nsets = 2) {
-  const size_t nk = ngroups * g.nwin * (size_t)g.nbuck;
+  using CQ = typename prime_of<C>::T;  // the hash set's curve in a split-row launch
+  if (g.split && (std::is_same<C, CQ>::value || nsets != 2 || g.halves != 2)) return hipErrorInvalidValue;
+  const size_t nk = ngroups * msm_rows(g) * (size_t)g.nbuck;
   constexpr size_t jw = 3 * C::EW;
   uint32_t* bB = ws.buckets + nk * jw;
   uint32_t* pB = ws.part + msm_nchunks(ws.max_entries) * 2 * jw;
@@ -1018,18 +1117,23 @@ static hipError_t msm28(const msm_geom& g, size_t ngroups, const uint32_t* S, co
     hipLaunchKernelGGL((k_msm_bucket28<C, true>), dim3(nblk(nch, 256)), dim3(256), 0, st, ws.off, ws.list, nk, L, S, ws.buckets,
                        ws.part, ws.meta, skip, g.half_stride);
     hipLaunchKernelGGL(k_msm_bucket_fix28<C>, dim3(nblk(nch, 256)), dim3(256), 0, st, ws.off, nk, L, ws.meta, ws.part, ws.buckets);
-    if (nsets == 2) {
+    if (nsets == 2 && !g.split) {
       hipLaunchKernelGGL((k_msm_bucket28<C, true>), dim3(nblk(nch, 256)), dim3(256), 0, st, ws.off, ws.list, nk, L, Q, bB, pB,
                          ws.meta, skip, g.half_stride);
       hipLaunchKernelGGL(k_msm_bucket_fix28<C>, dim3(nblk(nch, 256)), dim3(256), 0, st, ws.off, nk, L, ws.meta, pB, bB);
+    } else if (nsets == 2) {
+      hipLaunchKernelGGL((k_msm_bucket28<CQ, true>), dim3(nblk(nch, 256)), dim3(256), 0, st, ws.off, ws.list, nk, L, Q, bB, pB,
+                         ws.meta, skip, g.half_stride);
+      hipLaunchKernelGGL(k_msm_bucket_fix28<CQ>, dim3(nblk(nch, 256)), dim3(256), 0, st, ws.off, nk, L, ws.meta, pB, bB);
     }
   }
-  const size_t rows = ngroups * g.nwin, ngw = (size_t)nsets * rows;
+  const size_t rows = ngroups * msm_rows(g), ngw = (size_t)nsets * rows;
+  const size_t prime_from = g.split ? rows : NO_PRIME;
   const unsigned sb = few_waves_block(ngw * g.nseg);
   hipLaunchKernelGGL(k_msm_segsum28<C>, dim3(nblk(ngw * g.nseg, sb)), dim3(sb), 0, st, ws.buckets, ws.off, g, ngw, rows, ws.segs,
-                     ws.runs);
+                     ws.runs, prime_from);
   if (g.nseg > 1)
-    hipLaunchKernelGGL(k_msm_segoff28<C>, dim3(nblk(ngw * g.nseg, sb)), dim3(sb), 0, st, g, ngw, ws.segs, ws.runs);
+    hipLaunchKernelGGL(k_msm_segoff28<C>, dim3(nblk(ngw * g.nseg, sb)), dim3(sb), 0, st, g, ngw, ws.segs, ws.runs, prime_from);
   // row sums: ws.runs (free after the offsets) when a row's lanes fit one wave; else the waves' partials go to ws.runs
   // and the row sums to ws.segs
   // G: 8 when the rows' segments are many (the additions' count matters: the bisection's and the tbls per-signer
@@ -1048,15 +1152,23 @@ static hipError_t msm28(const msm_geom& g, size_t ngroups, const uint32_t* S, co
   const uint32_t* rowsum = ws.runs;
   if (g.nseg > 1)
     hipLaunchKernelGGL(k_msm_rowtree28<C>, dim3(nblk(ngw * lpr, few_waves_block(ngw * lpr))), dim3(few_waves_block(ngw * lpr)), 0,
-                       st, ws.segs, g.nseg, G, ngw, lpr, span, ws.runs);
+                       st, ws.segs, g.nseg, G, ngw, lpr, span, ws.runs, prime_from);
   else
     rowsum = ws.segs;  // one segment per row: its value is the row sum
   if (lpr > 64) {
     const uint32_t parts = lpr / 64;
     uint32_t pspan = 1;
     while (pspan < parts) pspan *= 2;
-    hipLaunchKernelGGL(k_msm_rowred28<C>, dim3((unsigned)ngw), dim3(64), 0, st, ws.runs, parts, pspan, ws.segs);
+    hipLaunchKernelGGL(k_msm_rowred28<C>, dim3((unsigned)ngw), dim3(64), 0, st, ws.runs, parts, pspan, ws.segs, prime_from);
     rowsum = ws.segs;
+  }
+  if constexpr (!std::is_same<C, CQ>::value) {
+    if (g.split) {
+      hipLaunchKernelGGL(k_msm_iso_rows28, dim3(nblk(rows, 64)), dim3(64), 0, st, const_cast<uint32_t*>(rowsum), rows, rows);
+      hipLaunchKernelGGL(k_msm_windows28_split<C>, dim3(nblk(2 * nsets * ngroups, 64)), dim3(64), 0, st, rowsum, g,
+                         (size_t)nsets * ngroups, ws.out2);
+      return hipGetLastError();
+    }
   }
   hipLaunchKernelGGL(k_msm_windows28<C>, dim3(nblk(nsets * ngroups, 64)), dim3(64), 0, st, rowsum, g, nsets * ngroups, ws.out2);
   return hipGetLastError();
@@ -1099,6 +1211,8 @@ hipError_t launch_msm28_set(int sig_g2, const msm_geom& g, const uint32_t* pidx,
 // ones (every lane of a pair the same count, no idle half), the wave tree sums the lanes, k_msm_rowred28 the waves'
 // partials. c x 2^(c-2) additions per row (262k at c = 16) against the fold's ~2^c, on buckets that exist already.
 // An empty bucket is the identity and is never read, like the reduction's.
+// With split rows (msm_geom split) the first nwin rows hold each sigma_i under the digits of its a-half
+// alone (no phi(sigma_i) shares them): the same claim on a simpler sum, and the b-halves' rows are not tested.
 constexpr uint32_t SUB_G = 8;
 DH_DEV uint32_t sub_digit(uint32_t j, uint32_t b) { return ((j >> b) << (b + 1)) | (1u << b) | (j & ((1u << b) - 1)); }
 template <class C, bool EXACT>
@@ -1171,7 +1285,7 @@ static hipError_t sub_batch(const msm_geom& g, const msm_ws& ws, uint8_t* pass, 
   hipLaunchKernelGGL(k_sub_bits28<C>, dim3(nblk(nlanes, blk)), dim3(blk), 0, st, ws.buckets, ws.off, g, lpp, ws.sub);
   uint32_t pspan = 1;
   while (pspan < parts) pspan *= 2;
-  hipLaunchKernelGGL(k_msm_rowred28<C>, dim3(npairs), dim3(64), 0, st, ws.sub, parts, pspan, tpts);
+  hipLaunchKernelGGL(k_msm_rowred28<C>, dim3(npairs), dim3(64), 0, st, ws.sub, parts, pspan, tpts, NO_PRIME);
   hipLaunchKernelGGL(k_sub_test28<C>, dim3(nblk(npairs, 64)), dim3(64), 0, st, tpts, npairs, pass, sub_pass);
   return hipGetLastError();
 }

@@ -8,11 +8,14 @@
 //                  likewise: k_dec_sig_g2 without k_sub_sig_g2)
 //   k_prep_msg     DigestBeacon + hash_to_curve without cofactor clearing               [A2, A3, A4b]
 //                  (a large local G1 batch: k_round_g1_ride does this and the decode above on one lane, the hash
-//                  point's inversion riding the decode's square-root chain)
+//                  point's inversion riding the decode's square-root chain; by default it also leaves the
+//                  hash's 11-isogeny to the MSM and writes the MSM's 28-bit points itself)
 //   k_scalars      128-bit random-linear-combination scalars r_i = SHA-256(seed || i)   [batching, new]
 //   MSM (grouped Pippenger, shared sort for both point sets):
 //     k_msm_hist -> scan -> k_msm_scatter -> k_msm_bucket28<S>, k_msm_bucket28<Q> -> k_msm_segsum28 -> k_msm_tree28
 //     -> k_msm_windows       per group g:  A_g = sum r_i sigma_i,  B_g = sum r_i Q_i
+//     (level 0 of the batch above: the hash set stays on E1' up to its row sums, k_msm_iso_rows28 ->
+//     k_msm_windows28_split)
 //   k_group_check  e(A_g, g2) == e([h_eff] B_g, pk)  (or the G2-signature mirror), one lane per group [A4c]
 //   k_leaf_check   per-round 2-pairing check for rounds left in failing groups (bisection leaves)
 // All scheme semantics follow /root/reference/crypto/schemes.go:70-72 (VerifyBeacon) and the kyber /
@@ -264,9 +267,15 @@ __global__ __launch_bounds__(256, occ<fp>::W) void k_prep_msg_g1(const uint64_t*
 // share x (never for hashed inputs) the chain rides on c = 1 and the lane takes h2c_g1_map in a divergent branch, on
 // the u0, u1 it parked in its q_out slot (24 of the slot's 36 words, as the G2 passes park theirs): with the branch
 // recomputing them from the message the kernel's scratch frame was 1,088 B a lane against 688.
+// LATE: the isogeny is left to the batch, once per MSM row sum. The lane stops after g1_sum_post and
+// stores the affine E1' point in the MSM's 28-bit form at q28 + 32 i, and sigma there too (s28 + 32 i): no
+// k_msm_prep28 launch follows. q_out then holds only the parking slot. When the two SSWU points share x the divergent
+// branch doubles on E1' (the curve's own A', one in-lane inversion) or, for opposite points, rejects the round: the
+// identity is no valid signature's message (k_msm_prep28's verdict for it on the other path).
+template <bool LATE>
 DH_DEV void round_g1_ride(const fp& u0, const fp& u1, bool msg_ok, const uint8_t* __restrict__ s, size_t i,
                           uint8_t* __restrict__ status, uint32_t* __restrict__ sig_aff, uint8_t* __restrict__ rand_out,
-                          uint32_t* __restrict__ q_out) {
+                          uint32_t* __restrict__ q_out, uint32_t* __restrict__ s28, uint32_t* __restrict__ q28) {
   st_f<fp>(q_out + 36 * i, u0);
   st_f<fp>(q_out + 36 * i + 12, u1);
   g1_sum_mid m;
@@ -285,23 +294,50 @@ DH_DEV void round_g1_ride(const fp& u0, const fp& u1, bool msg_ok, const uint8_t
     }
     status[i] = msg_ok ? st : (uint8_t)DEC_BAD;
     st_aff_aos<fp>(sig_aff, i, a);
+    if constexpr (LATE) {
+      st28(s28 + 2 * W28 * i, f28_from_fp(a.x));
+      st28(s28 + 2 * W28 * i + W28, f28_from_fp(a.y));
+    }
   }
-  if (distinct) {
-    st_jac_aos<fp>(q_out, i, iso11_aff(g1_sum_post(m, inv_c)));
+  if constexpr (LATE) {
+    aff<fp> q;
+    if (distinct) {
+      q = g1_sum_post(m, inv_c);
+    } else {
+      fp v0, v1;
+      ld_f<fp>(v0, q_out + 36 * i);
+      ld_f<fp>(v1, q_out + 36 * i + 12);
+      const swu_out<fp> p0 = sswu_g1(v0);
+      const fp y1 = sswu_g1(v1).y;
+      if (fp_eq(p0.y, y1)) {
+        q = e1p_dbl_aff(p0);
+      } else {
+        q = aff<fp>{fp{}, fp{}};
+        status[i] = DEC_BAD;
+      }
+    }
+    st28(q28 + 2 * W28 * i, f28_from_fp(q.x));
+    st28(q28 + 2 * W28 * i + W28, f28_from_fp(q.y));
   } else {
-    fp v0, v1;
-    ld_f<fp>(v0, q_out + 36 * i);
-    ld_f<fp>(v1, q_out + 36 * i + 12);
-    st_jac_aos<fp>(q_out, i, h2c_g1_map(v0, v1));
+    if (distinct) {
+      st_jac_aos<fp>(q_out, i, iso11_aff(g1_sum_post(m, inv_c)));
+    } else {
+      fp v0, v1;
+      ld_f<fp>(v0, q_out + 36 * i);
+      ld_f<fp>(v1, q_out + 36 * i + 12);
+      st_jac_aos<fp>(q_out, i, h2c_g1_map(v0, v1));
+    }
   }
 }
 
+template <bool LATE>
 __global__ __launch_bounds__(256, occ<fp>::W) void k_round_g1_ride(const uint64_t* __restrict__ rounds, const uint8_t* __restrict__ prevs,
                                                               size_t prev_stride, const uint32_t* __restrict__ prev_lens,
                                                               const uint8_t* __restrict__ msgs32, size_t n, int chained, int dst_id,
                                                               const uint8_t* __restrict__ sigs, size_t stride,
                                                               uint8_t* __restrict__ status, uint32_t* __restrict__ sig_aff,
-                                                              uint8_t* __restrict__ rand_out, uint32_t* __restrict__ q_out) {
+                                                              uint8_t* __restrict__ rand_out, uint32_t* __restrict__ q_out,
+                                                              uint32_t* __restrict__ s28, uint32_t* __restrict__ q28) {
   size_t i = gtid();
   if (i >= n) return;
   sha_h d;
@@ -310,23 +346,25 @@ __global__ __launch_bounds__(256, occ<fp>::W) void k_round_g1_ride(const uint64_
   else msg_ok = beacon_digest(d, rounds, prevs, prev_stride, prev_lens, chained, i);
   uint32_t b[4][8];
   xmd32<4>(b, d, dst_id);
-  round_g1_ride(fp_from_be512(b[0], b[1]), fp_from_be512(b[2], b[3]), msg_ok, sigs + i * stride, i, status, sig_aff, rand_out,
-                q_out);
+  round_g1_ride<LATE>(fp_from_be512(b[0], b[1]), fp_from_be512(b[2], b[3]), msg_ok, sigs + i * stride, i, status, sig_aff,
+                      rand_out, q_out, s28, q28);
 }
 
 // the test entry's kernels (dh_g1_round_prep_debug): round_g1_ride from given u0, u1 (2 x 48 big-endian bytes a round,
 // canonical), then sigma and the hash point as canonical affine x || y (2 x 48 big-endian bytes each; the identity,
 // and a rejected signature, as zeros)
+template <bool LATE>
 __global__ __launch_bounds__(256, occ<fp>::W) void k_round_g1_ride_debug(const uint8_t* __restrict__ u, size_t n,
                                                                     const uint8_t* __restrict__ sigs, size_t stride,
                                                                     uint8_t* __restrict__ status, uint32_t* __restrict__ sig_aff,
-                                                                    uint32_t* __restrict__ q_out) {
+                                                                    uint32_t* __restrict__ q_out, uint32_t* __restrict__ s28,
+                                                                    uint32_t* __restrict__ q28) {
   size_t i = gtid();
   if (i >= n) return;
   fp u0, u1;
   be48_words(u0.v, u + 96 * i, false);
   be48_words(u1.v, u + 96 * i + 48, false);
-  round_g1_ride(fp_to_mont(u0), fp_to_mont(u1), true, sigs + i * stride, i, status, sig_aff, nullptr, q_out);
+  round_g1_ride<LATE>(fp_to_mont(u0), fp_to_mont(u1), true, sigs + i * stride, i, status, sig_aff, nullptr, q_out, s28, q28);
 }
 __global__ __launch_bounds__(64) void k_round_g1_debug_out(size_t n, const uint32_t* __restrict__ sig_aff,
                                                            const uint32_t* __restrict__ q_pts, uint8_t* __restrict__ sig_out,
@@ -341,6 +379,29 @@ __global__ __launch_bounds__(64) void k_round_g1_debug_out(size_t n, const uint3
   if (!jac_is_inf(q)) a = jac_to_aff(q);
   st_be48(q_out + 96 * i, fp_from_mont(a.x));
   st_be48(q_out + 96 * i + 48, fp_from_mont(a.y));
+}
+
+// the LATE form's outputs (dh_g1_round_prep_late_debug): sigma and the E1' point read back from the 28-bit arrays the
+// MSM reads, canonical affine x || y; the identity (a rejected round) is stored as zeros
+__global__ __launch_bounds__(64) void k_round_g1_late_debug_out(size_t n, const uint32_t* __restrict__ s28,
+                                                                const uint32_t* __restrict__ q28, uint8_t* __restrict__ sig_out,
+                                                                uint8_t* __restrict__ q_out) {
+  size_t i = gtid();
+  if (i >= n) return;
+  st_be48(sig_out + 96 * i, fp_from_mont(f28_to_fp(ld28(s28 + 2 * W28 * i))));
+  st_be48(sig_out + 96 * i + 48, fp_from_mont(f28_to_fp(ld28(s28 + 2 * W28 * i + W28))));
+  st_be48(q_out + 96 * i, fp_from_mont(f28_to_fp(ld28(q28 + 2 * W28 * i))));
+  st_be48(q_out + 96 * i + 48, fp_from_mont(f28_to_fp(ld28(q28 + 2 * W28 * i + W28))));
+}
+
+// the LATE form's fallback (verify_core, level 0 did not end the batch): the isogeny per round after all, into the
+// Jacobian hash points the other form writes; k_msm_prep28 follows and rejects a point in the isogeny's kernel (Z = 0)
+__global__ __launch_bounds__(256, occ<fp>::W) void k_iso_late_fallback(size_t n, const uint8_t* __restrict__ status,
+                                                                  const uint32_t* __restrict__ q28, uint32_t* __restrict__ q_pts) {
+  size_t i = gtid();
+  if (i >= n || status[i] != DEC_OK) return;
+  const aff<fp> q{f28_to_fp(ld28(q28 + 2 * W28 * i)), f28_to_fp(ld28(q28 + 2 * W28 * i + W28))};
+  st_jac_aos<fp>(q_pts, i, iso11_aff(q));
 }
 
 // G2 in three passes. The G2 map keeps more Fp2 values live than one lane's 256 VGPRs hold (fused, the kernel
@@ -582,17 +643,45 @@ hipError_t launch_round_g1_ride(const uint64_t* rounds, const uint8_t* prevs, si
                                 const uint8_t* msgs32, size_t n, int chained, int dst_id, const uint8_t* sigs, size_t stride,
                                 uint8_t* status, uint32_t* sig_aff, uint8_t* rand_out, uint32_t* q_out, hipStream_t st) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_round_g1_ride, dim3(nblk(n, 256)), dim3(256), 0, st, rounds, prevs, prev_stride, prev_lens, msgs32, n,
-                     chained, dst_id, sigs, stride, status, sig_aff, rand_out, q_out);
+  hipLaunchKernelGGL(k_round_g1_ride<false>, dim3(nblk(n, 256)), dim3(256), 0, st, rounds, prevs, prev_stride, prev_lens, msgs32, n,
+                     chained, dst_id, sigs, stride, status, sig_aff, rand_out, q_out, (uint32_t*)nullptr, (uint32_t*)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t launch_round_g1_ride_late(const uint64_t* rounds, const uint8_t* prevs, size_t prev_stride, const uint32_t* prev_lens,
+                                     const uint8_t* msgs32, size_t n, int chained, int dst_id, const uint8_t* sigs, size_t stride,
+                                     uint8_t* status, uint32_t* sig_aff, uint8_t* rand_out, uint32_t* q_out, uint32_t* s28,
+                                     uint32_t* q28, hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(k_round_g1_ride<true>, dim3(nblk(n, 256)), dim3(256), 0, st, rounds, prevs, prev_stride, prev_lens, msgs32, n,
+                     chained, dst_id, sigs, stride, status, sig_aff, rand_out, q_out, s28, q28);
+  return hipGetLastError();
+}
+
+hipError_t launch_iso_late_fallback(size_t n, const uint8_t* status, const uint32_t* q28, uint32_t* q_pts, hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(k_iso_late_fallback, dim3(nblk(n, 256)), dim3(256), 0, st, n, status, q28, q_pts);
   return hipGetLastError();
 }
 
 hipError_t launch_round_g1_ride_debug(const uint8_t* u, const uint8_t* sigs, size_t n, uint8_t* status, uint32_t* sig_aff,
                                       uint32_t* q_pts, uint8_t* sig_out, uint8_t* q_out, hipStream_t st) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(k_round_g1_ride_debug, dim3(nblk(n, 256)), dim3(256), 0, st, u, n, sigs, (size_t)48, status, sig_aff, q_pts);
+  hipLaunchKernelGGL(k_round_g1_ride_debug<false>, dim3(nblk(n, 256)), dim3(256), 0, st, u, n, sigs, (size_t)48, status, sig_aff,
+                     q_pts, (uint32_t*)nullptr, (uint32_t*)nullptr);
   hipLaunchKernelGGL(k_round_g1_debug_out, dim3(nblk(n, 64)), dim3(64), 0, st, n, (const uint32_t*)sig_aff,
                      (const uint32_t*)q_pts, sig_out, q_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_round_g1_ride_late_debug(const uint8_t* u, const uint8_t* sigs, size_t n, uint8_t* status, uint32_t* sig_aff,
+                                           uint32_t* q_pts, uint32_t* s28, uint32_t* q28, uint8_t* sig_out, uint8_t* q_out,
+                                           hipStream_t st) {
+  if (!n) return hipSuccess;
+  hipLaunchKernelGGL(k_round_g1_ride_debug<true>, dim3(nblk(n, 256)), dim3(256), 0, st, u, n, sigs, (size_t)48, status, sig_aff,
+                     q_pts, s28, q28);
+  hipLaunchKernelGGL(k_round_g1_late_debug_out, dim3(nblk(n, 64)), dim3(64), 0, st, n, (const uint32_t*)s28, (const uint32_t*)q28,
+                     sig_out, q_out);
   return hipGetLastError();
 }
 

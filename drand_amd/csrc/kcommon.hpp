@@ -78,6 +78,28 @@ DH_DEV void st_aff_aos(uint32_t* base, size_t i, const aff<F>& a) {
   st_f<F>(p + N, a.y);
 }
 
+// a lazily reduced 28-bit Fp element (fp28.hpp) in the MSM's arrays: 16 words (14 limbs + 2 pad: four 16-byte accesses)
+constexpr int W28 = 16;
+DH_DEV f28 ld28(const uint32_t* p) {
+  const uint4* q = (const uint4*)p;
+  f28 a;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const uint4 t = q[i];
+    a.l[4 * i] = t.x;
+    a.l[4 * i + 1] = t.y;
+    if (4 * i + 2 < 14) a.l[4 * i + 2] = t.z;
+    if (4 * i + 3 < 14) a.l[4 * i + 3] = t.w;
+  }
+  return a;
+}
+DH_DEV void st28(uint32_t* p, const f28& a) {
+  uint4* q = (uint4*)p;
+#pragma unroll
+  for (int i = 0; i < 4; i++)
+    q[i] = make_uint4(a.l[4 * i], a.l[4 * i + 1], 4 * i + 2 < 14 ? a.l[4 * i + 2] : 0u, 4 * i + 3 < 14 ? a.l[4 * i + 3] : 0u);
+}
+
 // add-2007-bl for two points held in memory (AoS Jacobian, 72 words each), coordinates loaded as they are needed;
 // Z3 = 2 Z1 Z2 h (= ((Z1 + Z2)^2 - Z1^2 - Z2^2) h). false (r unset) when x1 == x2, as jac_add_distinct.
 DH_DEV bool jac_add_distinct_mem(jac<fp2>& r, const uint32_t* P, const uint32_t* Q) {

@@ -25,8 +25,15 @@ struct msm_geom {
   uint32_t seglen;
   uint32_t halves;       // 1; 2 for the endomorphism split (G1 phi, G2 psi); 4 for the G2 four-part psi split
   uint32_t half_stride;  // point index offset of endo(P) (halves = 2) / of each psi power (halves = 4)
+  // 1 (halves = 2, G1 level 0 with the hash set on E1'): half h of a scalar keys window row h * nwin + w of
+  // its group and its entry is the point index itself: no image, the endomorphism is applied once to the sum of rows
+  // nwin .. 2 nwin - 1 (k_msm_windows28_split). Each half is recoded on its own, as for split = 0. half_stride stays
+  // the round count (the bucket pass's skip test).
+  uint32_t split = 0;
 };
 inline size_t msm_entries(const msm_geom& g, size_t m) { return m * (size_t)g.nwin * g.halves; }
+// window rows (of nbuck keys) per group
+__host__ __device__ inline uint32_t msm_rows(const msm_geom& g) { return (uint32_t)g.nwin * (g.split ? g.halves : 1u); }
 
 // device workspace of one MSM level (sized by the caller from msm_geom)
 struct msm_ws {
@@ -96,10 +103,25 @@ hipError_t launch_hash(int sig_g2, const uint64_t* rounds, const uint8_t* prevs,
 hipError_t launch_round_g1_ride(const uint64_t* rounds, const uint8_t* prevs, size_t prev_stride, const uint32_t* prev_lens,
                                 const uint8_t* msgs32, size_t n, int chained, int dst_id, const uint8_t* sigs, size_t stride,
                                 uint8_t* status, uint32_t* sig_aff, uint8_t* rand_out, uint32_t* q_out, hipStream_t st);
+// The same launch with the isogeny left to the batch: the hash point leaves as the affine sum of the two
+// SSWU points on E1', in the MSM's 28-bit form at q28 + 32 i, and sigma also at s28 + 32 i (launch_msm_prep28's layout
+// for the first n points; no images), for the rounds whose status is DEC_OK. q_out keeps only the u0, u1 parking
+// slots. A round whose two SSWU points are opposite (the identity; never for hashed inputs) is DEC_BAD.
+hipError_t launch_round_g1_ride_late(const uint64_t* rounds, const uint8_t* prevs, size_t prev_stride, const uint32_t* prev_lens,
+                                     const uint8_t* msgs32, size_t n, int chained, int dst_id, const uint8_t* sigs, size_t stride,
+                                     uint8_t* status, uint32_t* sig_aff, uint8_t* rand_out, uint32_t* q_out, uint32_t* s28,
+                                     uint32_t* q28, hipStream_t st);
+// the fallback to launch_round_g1_ride's arrays: q_pts[i] = the 11-isogeny's image of the E1' point at q28 + 32 i,
+// Jacobian, for the rounds whose status is DEC_OK (launch_msm_prep28 then refills s28 and q28)
+hipError_t launch_iso_late_fallback(size_t n, const uint8_t* status, const uint32_t* q28, uint32_t* q_pts, hipStream_t st);
 // the same per-round code from given u0 || u1 (96 canonical big-endian bytes a round) and 48-byte signatures; sig_out
 // and q_out: canonical affine x || y (96 bytes a round), zeros for the identity; sig_aff / q_pts: n x 24 / 36 words
 hipError_t launch_round_g1_ride_debug(const uint8_t* u, const uint8_t* sigs, size_t n, uint8_t* status, uint32_t* sig_aff,
                                       uint32_t* q_pts, uint8_t* sig_out, uint8_t* q_out, hipStream_t st);
+// launch_round_g1_ride_late's code the same way: q_out = the stored E1' point, s28 / q28: n x 32 words each
+hipError_t launch_round_g1_ride_late_debug(const uint8_t* u, const uint8_t* sigs, size_t n, uint8_t* status, uint32_t* sig_aff,
+                                           uint32_t* q_pts, uint32_t* s28, uint32_t* q28, uint8_t* sig_out, uint8_t* q_out,
+                                           hipStream_t st);
 // the same hash points for messages of any length, message i = msgs[msg_off[i] .. msg_off[i + 1]) (sign.Scheme.Verify
 // in batch: xmd_any, sha256.hpp); tmp: hash_tmp_bytes(sig_g2, n)
 hipError_t launch_hash_var(int sig_g2, const uint8_t* msgs, const uint32_t* msg_off, size_t n, int dst_id, uint32_t* q_out,

@@ -421,6 +421,15 @@ int dh_g1_round_prep_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uin
                            uint8_t* hash_out);
 
 /*
+ * Test entry: the same kernel in the form that leaves the hash's 11-isogeny to the batch (DRANDHIP_G1_ISO_LATE, the
+ * default for such a batch). Same inputs; sig_out and hash_out are read back from the 28-bit arrays the MSM reads:
+ * sigma as above, and hash_out the sum swu(u0) + swu(u1) on the isogenous curve E1' (RFC 9380 8.8.1) as canonical
+ * affine x || y, before the isogeny; zeros for the identity, whose round is rejected (status_out 0).
+ */
+int dh_g1_round_prep_late_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uint8_t* status_out, uint8_t* sig_out,
+                                uint8_t* hash_out);
+
+/*
  * Live kernel timing: when enabled, every device stage of the verification path is bracketed by HIP
  * events on the stream it is launched on; dh_profile_read writes a JSON object
  * {"stage": {"count": c, "total_ms": t}, ...} into buf (returns the full length). dh_profile resets.
