@@ -23,6 +23,7 @@ DH_ENOBEACON = -9
 DH_NODE_CHECKED = 2
 DH_DEFERRED = 1
 DH_STORE_TRIMMED, DH_STORE_UNTRIMMED, DH_STORE_AUTO = 0, 1, 2
+DH_PATCH_DELETE = 0xFFFFFFFF
 
 # every symbol declared in include/drandhip.h, with (restype, argtypes)
 _c = ctypes
@@ -78,6 +79,9 @@ SIGNATURES = {
     "dh_store_beacons_device": (_c.c_int, [_P, _c.c_uint64, _c.c_uint64, _c.c_size_t, _c.c_size_t, _P, _P, _P, _P, _P, _P,
                                            _c.c_size_t, _P, _P, _c.c_size_t, _P, _P]),
     "dh_store_deferred": (_c.c_int, [_P, _c.c_uint64, _c.c_uint64, _P, _c.c_size_t, _P]),
+    "dh_bolt_write_trimmed_device": (_c.c_int, [_P, _P, _c.c_size_t, _P, _c.c_size_t, _c.c_uint32, _P, _c.c_size_t, _P, _P, _P]),
+    "dh_store_save_trimmed": (_c.c_int, [_P, _c.c_uint64, _c.c_uint64, _P, _P, _c.c_size_t, _P, _c.c_size_t, _c.c_uint32, _P,
+                                         _c.c_size_t, _P, _P, _c.c_size_t, _P, _P]),
     "dh_profile": (_c.c_int, [_c.c_int]),
     "dh_profile_read": (_c.c_int, [_c.c_char_p, _c.c_size_t]),
     "dh_last_error_string": (_c.c_char_p, []),

@@ -33,6 +33,7 @@
 
 #include "../../include/drandhip.h"
 #include "bolt.hpp"
+#include "bolt_write.hpp"
 #include "kernels.hpp"
 
 namespace {
@@ -2930,6 +2931,18 @@ struct prof_wall {  // host wall time of one store stage (each ends in a stream 
   }
 };
 
+// device scratch of one trimmed-store write
+struct write_ws {
+  dbuf need, sums, scan_tmp, err, leaves, image, keys;
+  // dh_store_save_trimmed: the uploaded patches, the merge's slots and the merged columns
+  dbuf p_rounds, p_rows, p_lens, flag, lb, pos, hit, o_rounds, o_rows, o_lens, o_src, unl;
+  void release() {
+    for (dbuf* b : {&need, &sums, &scan_tmp, &err, &leaves, &image, &keys, &p_rounds, &p_rows, &p_lens, &flag, &lb, &pos, &hit,
+                    &o_rounds, &o_rows, &o_lens, &o_src, &unl})
+      b->release();
+  }
+};
+
 struct dh_store {
   std::mutex mu;                    // calls on one handle are serialised
   std::atomic<bool> retire{false};  // dh_shutdown ran while a call held the handle: that call (or the next) releases
@@ -2948,7 +2961,9 @@ struct dh_store {
   std::vector<uint8_t> h_defer;
   std::vector<uint8_t> h_bad;
   std::vector<uint64_t> h_rounds, h_missing;
+  write_ws wws;  // dh_store_save_trimmed
   void release() {
+    wws.release();
     for (dbuf* b : {&d_file, &d_leaves, &d_info, &err, &cnt, &base, &scan_tmp, &rounds, &rows, &lens, &miss_prev, &gap, &moff,
                     &missing, &verdict, &bad, &d_jinfo, &prevs, &prev_lens, &defer})
       b->release();
@@ -3537,6 +3552,235 @@ int dh_store_deferred(dh_store* s, uint64_t first, uint64_t last, uint64_t* out,
   }
   *n_out = n;
   if (n > cap) return fail(DH_EINVAL, "%zu deferred records, room for %zu", n, cap);
+  return DH_OK;
+}
+
+}  // extern "C"
+
+// ---- trimmed bbolt store files written from device columns: bolt_write.hpp decides every byte; the
+// device packs the leaf pages (k_bolt_write.hip), the host plans them from the scanned record sizes and writes the
+// branch levels and pages 0-3.
+
+// Entered with the device set. With cap too small (cap 0 sizes only): DH_EINVAL, *len_out set, nothing written.
+static int bolt_write_core(hipStream_t st, write_ws& ws, const uint64_t* d_rounds, const uint8_t* d_rows, size_t stride,
+                           const uint32_t* d_lens, size_t n, uint32_t P, uint8_t* image_out, size_t cap, size_t* len_out,
+                           uint64_t stats[3], const char* const stage[3]) {
+  using namespace dh::boltw;
+  *len_out = 0;
+  if (!n) return fail(DH_ENOBEACON, "no beacon to write: an empty store is not written");
+  if (n + 2 > (size_t)4096 * 4096) return fail(DH_EINVAL, "%zu rows: at most 16M rows per call", n);
+  std::vector<leaf_desc> leaves;
+  uint64_t leaf_end = FIRST_LEAF_PAGE, pages = 0;
+  {
+    prof_wall p(stage[0]);
+    std::vector<uint32_t> sums(n + 1);
+    uint32_t err_word = 0;
+    HIP_TRY(ws.need.ensure(n * 4));
+    HIP_TRY(ws.sums.ensure((n + 1) * 4));
+    HIP_TRY(ws.scan_tmp.ensure((n / 4096 + 2) * 4));
+    HIP_TRY(ws.err.ensure(4));
+    HIP_TRY(hipMemsetAsync(ws.err.p, 0, 4, st));
+    HIP_TRY(dh::launch_bolt_need(d_rounds, d_lens, n, stride, ws.need.as<uint32_t>(), ws.err.as<uint32_t>(), st));
+    HIP_TRY(dh::launch_scan(ws.need.as<uint32_t>(), n, ws.sums.as<uint32_t>(), ws.scan_tmp.as<uint32_t>(), st));
+    HIP_TRY(hipMemcpyAsync(sums.data(), ws.sums.p, (n + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err_word, ws.err.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err_word) return fail(DH_EINVAL, "rounds not strictly ascending, or a value longer than the row stride %zu", stride);
+    // the greedy leaf boundaries: a host walk over the sums (8 bytes a row with the copy, well below the pack's time)
+    for (uint64_t s = 0; s < n;) {
+      leaf_desc L;
+      s += plan_leaf(sums.data(), n, s, P, leaf_end, &L);
+      leaf_end += L.span;
+      leaves.push_back(L);
+    }
+    pages = leaf_end + branch_pages(leaves.size(), P);
+  }
+  const uint64_t bytes = pages * P;
+  *len_out = (size_t)bytes;
+  if (stats) {
+    stats[0] = n;
+    stats[1] = leaves.size();
+    stats[2] = pages;
+  }
+  if (bytes > store_max_bytes())
+    return fail(DH_ENOMEM, "store image of %llu bytes exceeds DRANDHIP_STORE_MAX_BYTES (%zu)", (unsigned long long)bytes, store_max_bytes());
+  if (cap < bytes || !image_out) return fail(DH_EINVAL, "store image of %llu bytes, room for %zu", (unsigned long long)bytes, cap);
+  const size_t nl = leaves.size();
+  const uint64_t leaf_bytes = (leaf_end - FIRST_LEAF_PAGE) * P;
+  std::vector<uint64_t> keys(nl), pgids(nl);
+  {
+    prof_wall p(stage[1]);
+    HIP_TRY(ws.leaves.ensure(nl * sizeof(leaf_desc)));
+    HIP_TRY(ws.image.ensure(leaf_bytes));
+    HIP_TRY(ws.keys.ensure(nl * 8));
+    HIP_TRY(hipMemcpyAsync(ws.leaves.p, leaves.data(), nl * sizeof(leaf_desc), hipMemcpyHostToDevice, st));
+    timed_launches tl(st);
+    HIP_TRY(tl.run("k_bolt_pack", [&] {
+      return dh::launch_bolt_pack(ws.leaves.p, nl, d_rounds, d_rows, stride, d_lens, P, ws.image.as<uint8_t>(), ws.keys.as<uint64_t>(), st);
+    }));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  prof_wall p(stage[2]);
+  HIP_TRY(hipMemcpyAsync(image_out + FIRST_LEAF_PAGE * P, ws.image.p, leaf_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(keys.data(), ws.keys.p, nl * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (size_t i = 0; i < nl; i++) pgids[i] = leaves[i].page;
+  finish_image(image_out, P, pages, leaf_end, keys.data(), pgids.data(), nl);
+  return DH_OK;
+}
+
+extern "C" {
+
+int dh_bolt_write_trimmed_device(const uint64_t* d_rounds, const uint8_t* d_rows, size_t row_stride, const uint32_t* d_lens, size_t n,
+                                 uint32_t page_size, uint8_t* image_out, size_t cap, size_t* len_out, uint64_t stats_out[3],
+                                 void* hip_stream) {
+  if (!len_out) return fail(DH_EINVAL, "null argument");
+  *len_out = 0;
+  if (!dh::boltw::page_size_ok(page_size)) return fail(DH_EINVAL, "page size %u: a power of two from 256 to 65536", page_size);
+  if (!n) return fail(DH_ENOBEACON, "no beacon to write: an empty store is not written");
+  if (!d_rounds || !d_lens || (row_stride && !d_rows) || (cap && !image_out)) return fail(DH_EINVAL, "null argument");
+  int rc = ensure_device();
+  if (rc) return rc;
+  if (hip_stream) HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));  // the columns may still be written there
+  hipStream_t st = nullptr;
+  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  write_ws ws;
+  static const char* const stage[3] = {"bolt_write_plan", "bolt_write_pack", "bolt_write_download"};
+  rc = bolt_write_core(st, ws, d_rounds, d_rows, row_stride, d_lens, n, page_size, image_out, cap, len_out, stats_out, stage);
+  ws.release();
+  (void)hipStreamDestroy(st);
+  return rc;
+}
+
+int dh_store_save_trimmed(dh_store* s, uint64_t first, uint64_t last, const uint64_t* patch_rounds, const uint8_t* patch_sigs,
+                          size_t patch_stride, const uint32_t* patch_lens, size_t n_patch, uint32_t page_size, uint8_t* image_out,
+                          size_t cap, size_t* len_out, uint64_t* unlinked_out, size_t unlinked_cap, size_t* n_unlinked_out,
+                          uint64_t stats_out[6]) {
+  if (!s || !len_out || !n_unlinked_out || (cap && !image_out) || (unlinked_cap && !unlinked_out)) return fail(DH_EINVAL, "null argument");
+  *len_out = 0;
+  *n_unlinked_out = 0;
+  if (!dh::boltw::page_size_ok(page_size)) return fail(DH_EINVAL, "page size %u: a power of two from 256 to 65536", page_size);
+  if (n_patch > ((size_t)1 << 20)) return fail(DH_EINVAL, "%zu patches: at most 2^20", n_patch);
+  if (n_patch && (!patch_rounds || !patch_lens)) return fail(DH_EINVAL, "null patch list");
+  if (patch_stride > ((size_t)1 << 20)) return fail(DH_EINVAL, "patch stride %zu above 1 MiB", patch_stride);
+  uint32_t patch_longest = 0;
+  for (size_t i = 0; i < n_patch; i++) {
+    if (patch_rounds[i] < first || patch_rounds[i] > last || (i && patch_rounds[i - 1] >= patch_rounds[i]))
+      return fail(DH_EINVAL, "patch %zu (round %llu): patches are strictly ascending and inside [first, last]", i,
+                  (unsigned long long)patch_rounds[i]);
+    if (patch_lens[i] == DH_PATCH_DELETE) continue;
+    if (patch_lens[i] > patch_stride || (patch_lens[i] && !patch_sigs))
+      return fail(DH_EINVAL, "patch %zu: %u bytes, patch stride %zu", i, patch_lens[i], patch_stride);
+    patch_longest = std::max(patch_longest, patch_lens[i]);
+  }
+  store_guard g(s);
+  int rc = store_enter(s);
+  if (rc) return rc;
+  write_ws& ws = s->wws;
+  const bool json = s->format == DH_STORE_UNTRIMMED;
+  size_t n_out = 0, n_unl = 0, n_hit = 0, n_ins = 0, o_stride = 4;
+  {
+    prof_wall p("store_save_merge");
+    size_t lo, nw, total;
+    uint32_t longest;
+    if ((rc = store_window(s, first, last, &lo, &nw, &total, &longest))) return rc;
+    if (total + n_patch + 3 > (size_t)4096 * 4096) return fail(DH_EINVAL, "%zu rows and %zu patches: at most 16M per call", total, n_patch);
+    if (json) longest = window_longest_json(s, lo, nw);
+    const size_t stride = std::max<size_t>(4, ((size_t)longest + 3) & ~(size_t)3);
+    if (stride > ((size_t)1 << 20)) return fail(DH_EINVAL, "a %u-byte record in rounds %llu..%llu: keep the host reader", longest,
+                                                (unsigned long long)first, (unsigned long long)last);
+    HIP_TRY(s->rounds.ensure(total * 8 + 8));
+    HIP_TRY(s->rows.ensure(total * stride + 8));
+    HIP_TRY(s->lens.ensure(total * 4 + 4));
+    if (json) {
+      HIP_TRY(s->defer.ensure(total + 8));
+      HIP_TRY(s->prevs.ensure(total * stride + 8));
+      HIP_TRY(s->prev_lens.ensure(total * 4 + 4));
+      const dh::json_cols c{s->rounds.as<uint64_t>(), s->defer.as<uint8_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
+                            s->prevs.as<uint8_t>(), s->prev_lens.as<uint32_t>(), (uint32_t)stride, (uint32_t)stride, total};
+      if ((rc = store_gather_json(s, lo, nw, total, first, last, c, nullptr, 0))) return rc;
+    } else if ((rc = store_gather(s, lo, nw, total, first, last, stride, s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(),
+                                  s->lens.as<uint32_t>(), total, nullptr, 0))) {
+      return rc;
+    }
+    // the patches, uploaded as given
+    const size_t slots = total + n_patch;
+    HIP_TRY(ws.p_rounds.ensure(n_patch * 8 + 8));
+    HIP_TRY(ws.p_lens.ensure(n_patch * 4 + 4));
+    HIP_TRY(ws.p_rows.ensure(n_patch * patch_stride + 8));
+    HIP_TRY(ws.flag.ensure(slots * 4 + 4));
+    HIP_TRY(ws.lb.ensure(slots * 4 + 4));
+    HIP_TRY(ws.pos.ensure((slots + 1) * 4));
+    HIP_TRY(ws.scan_tmp.ensure((slots / 4096 + 2) * 4));
+    HIP_TRY(ws.hit.ensure(n_patch + 8));
+    HIP_TRY(ws.err.ensure(4));
+    if (n_patch) {
+      HIP_TRY(hipMemcpyAsync(ws.p_rounds.p, patch_rounds, n_patch * 8, hipMemcpyHostToDevice, s->st));
+      HIP_TRY(hipMemcpyAsync(ws.p_lens.p, patch_lens, n_patch * 4, hipMemcpyHostToDevice, s->st));
+      if (patch_sigs && patch_stride)
+        HIP_TRY(hipMemcpyAsync(ws.p_rows.p, patch_sigs, n_patch * patch_stride, hipMemcpyHostToDevice, s->st));
+    }
+    HIP_TRY(hipMemsetAsync(ws.err.p, 0, 4, s->st));
+    const dh::merge_in m{s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
+                         json ? s->defer.as<uint8_t>() : nullptr, total, (uint32_t)stride, ws.p_rounds.as<uint64_t>(),
+                         ws.p_rows.as<uint8_t>(), ws.p_lens.as<uint32_t>(), n_patch, (uint32_t)patch_stride};
+    if (!slots) return fail(DH_ENOBEACON, "no beacon stored in rounds %llu..%llu", (unsigned long long)first, (unsigned long long)last);
+    HIP_TRY(dh::launch_bolt_merge(m, ws.flag.as<uint32_t>(), ws.lb.as<uint32_t>(), ws.hit.as<uint8_t>(), ws.err.as<uint32_t>(), s->st));
+    HIP_TRY(dh::launch_scan(ws.flag.as<uint32_t>(), slots, ws.pos.as<uint32_t>(), ws.scan_tmp.as<uint32_t>(), s->st));
+    uint32_t err_word = 0, tot = 0;
+    std::vector<uint8_t> hit(n_patch);
+    HIP_TRY(hipMemcpyAsync(&err_word, ws.err.p, 4, hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipMemcpyAsync(&tot, ws.pos.as<uint32_t>() + slots, 4, hipMemcpyDeviceToHost, s->st));
+    if (n_patch) HIP_TRY(hipMemcpyAsync(hit.data(), ws.hit.p, n_patch, hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));
+    if (err_word) {
+      g_err = "a deferred record in the range is not covered by a patch (dh_store_deferred lists them)";
+      return DH_DEFERRED;
+    }
+    for (uint8_t h : hit) {
+      n_hit += h == 1;
+      n_ins += h == 2;
+    }
+    n_out = tot;
+    if (!n_out) return fail(DH_ENOBEACON, "no beacon left to write in rounds %llu..%llu", (unsigned long long)first, (unsigned long long)last);
+    o_stride = std::max<size_t>(stride, ((size_t)patch_longest + 3) & ~(size_t)3);
+    HIP_TRY(ws.o_rounds.ensure(n_out * 8));
+    HIP_TRY(ws.o_rows.ensure(n_out * o_stride));
+    HIP_TRY(ws.o_lens.ensure(n_out * 4));
+    HIP_TRY(ws.o_src.ensure(n_out * 4));
+    const dh::merge_out o{ws.o_rounds.as<uint64_t>(), ws.o_rows.as<uint8_t>(), ws.o_lens.as<uint32_t>(), ws.o_src.as<uint32_t>(),
+                          (uint32_t)o_stride};
+    HIP_TRY(dh::launch_bolt_scatter(m, ws.flag.as<uint32_t>(), ws.lb.as<uint32_t>(), ws.pos.as<uint32_t>(), o, s->st));
+    if (json) {  // flag / pos are free again: the unlinked rows and their ranks
+      HIP_TRY(ws.flag.ensure(n_out * 4 + 4));
+      HIP_TRY(ws.pos.ensure((n_out + 1) * 4));
+      HIP_TRY(ws.unl.ensure(n_out * 8));
+      HIP_TRY(dh::launch_bolt_unlinked(o, n_out, s->prevs.as<uint8_t>(), (uint32_t)stride, s->prev_lens.as<uint32_t>(),
+                                       ws.flag.as<uint32_t>(), s->st));
+      HIP_TRY(dh::launch_scan(ws.flag.as<uint32_t>(), n_out, ws.pos.as<uint32_t>(), ws.scan_tmp.as<uint32_t>(), s->st));
+      HIP_TRY(dh::launch_bolt_compact(ws.o_rounds.as<uint64_t>(), ws.pos.as<uint32_t>(), n_out, ws.unl.as<uint64_t>(), s->st));
+      HIP_TRY(hipMemcpyAsync(&tot, ws.pos.as<uint32_t>() + n_out, 4, hipMemcpyDeviceToHost, s->st));
+      HIP_TRY(hipStreamSynchronize(s->st));
+      n_unl = tot;
+    } else {
+      HIP_TRY(hipStreamSynchronize(s->st));
+    }
+  }
+  *n_unlinked_out = n_unl;
+  const bool room = n_unl <= unlinked_cap;
+  uint64_t st3[3] = {0, 0, 0};
+  static const char* const stage[3] = {"store_save_plan", "store_save_pack", "store_save_download"};
+  rc = bolt_write_core(s->st, ws, ws.o_rounds.as<uint64_t>(), ws.o_rows.as<uint8_t>(), o_stride, ws.o_lens.as<uint32_t>(), n_out,
+                       page_size, room ? image_out : nullptr, room ? cap : 0, len_out, st3, stage);
+  if (stats_out) {
+    memcpy(stats_out, st3, sizeof st3);
+    stats_out[3] = n_unl;
+    stats_out[4] = n_hit;
+    stats_out[5] = n_ins;
+  }
+  if (!room) return fail(DH_EINVAL, "%zu unlinked rounds, room for %zu", n_unl, unlinked_cap);
+  if (rc) return rc;
+  if (n_unl) HIP_TRY(hipMemcpy(unlinked_out, ws.unl.p, n_unl * 8, hipMemcpyDeviceToHost));
   return DH_OK;
 }
 

@@ -312,6 +312,45 @@ hipError_t launch_bolt_gather_json(const uint8_t* file, const void* leaves, cons
 hipError_t launch_bolt_fold_json(const uint32_t* sig_lens, const uint8_t* deferred, const uint8_t* verdict, size_t n, uint32_t sig_len,
                                  uint8_t* bad, hipStream_t st);
 
+// verifier columns -> the leaf pages of a trimmed bbolt store (k_bolt_write.hip). need: the record
+// sizes 24 + lens[i] (then launch_scan), err_word set when rounds do not ascend or a length passes the stride. pack:
+// leaves = boltw::leaf_desc records (24 B, one wave each); `image` starts at page 4 and holds every leaf extent;
+// first_key[leaf] = its first round. merge: slots [0, n) the stored rows, [n, n + np) the ascending patches (p_lens
+// 0xFFFFFFFF = delete); flag / lb per slot (n + np words each), hit per patch, err_word set by a deferred row no patch
+// covers; then launch_scan over flag (pos, n + np + 1 words) and scatter into merge_out (stride a multiple of 4
+// holding every value; src = the stored row a merged row came from, 0xFFFFFFFF for a patch). unlinked: flag per
+// merged row (then launch_scan and compact: the flagged rounds, ascending).
+struct merge_in {
+  const uint64_t* rounds;
+  const uint8_t* rows;
+  const uint32_t* lens;
+  const uint8_t* defer;  // nullable
+  size_t n;
+  uint32_t stride;
+  const uint64_t* p_rounds;
+  const uint8_t* p_rows;
+  const uint32_t* p_lens;
+  size_t np;
+  uint32_t p_stride;
+};
+struct merge_out {
+  uint64_t* rounds;
+  uint8_t* rows;
+  uint32_t* lens;
+  uint32_t* src;
+  uint32_t stride;
+};
+hipError_t launch_bolt_need(const uint64_t* rounds, const uint32_t* lens, size_t n, uint64_t stride, uint32_t* need, uint32_t* err_word,
+                            hipStream_t st);
+hipError_t launch_bolt_pack(const void* leaves, size_t n_leaves, const uint64_t* rounds, const uint8_t* rows, uint64_t stride,
+                            const uint32_t* lens, uint32_t page_size, uint8_t* image, uint64_t* first_key, hipStream_t st);
+hipError_t launch_bolt_merge(const merge_in& m, uint32_t* flag, uint32_t* lb, uint8_t* hit, uint32_t* err_word, hipStream_t st);
+hipError_t launch_bolt_scatter(const merge_in& m, const uint32_t* flag, const uint32_t* lb, const uint32_t* pos, const merge_out& o,
+                               hipStream_t st);
+hipError_t launch_bolt_unlinked(const merge_out& o, size_t n_out, const uint8_t* prevs, uint32_t prev_stride, const uint32_t* prev_lens,
+                                uint32_t* flag, hipStream_t st);
+hipError_t launch_bolt_compact(const uint64_t* rounds, const uint32_t* off, size_t n, uint64_t* out, hipStream_t st);
+
 #ifdef DH_COUNT_PRODUCTS
 // counting build: field products executed since the last take, per translation unit (fp_mul28.hpp)
 hipError_t count_take_prep(unsigned long long* v);

@@ -20,6 +20,7 @@ store file, plus columns(first, last) for bulk ingestion.
 """
 import ctypes
 import json
+import os
 import struct
 
 import numpy as np
@@ -493,6 +494,138 @@ class DeviceBoltStore:
                 extra = self._resolve_deferred(scheme, pubkey, up_to, seed)
                 got = [rep for _k, rep in sorted([(k, k) for k in got] + extra, key=lambda t: t[0])]
             return got
+
+
+    # ---- writing
+    def stored_signature(self, round_):
+        """The signature stored for one round (untrimmed: the decoded Signature field), whatever its neighbours."""
+        raw = self._raw(int(round_))
+        return beacon_from_hexjson(raw).signature if self.untrimmed else raw
+
+    def save_trimmed(self, path, first=0, last=None, patches=None, page_size=4096):
+        """dh_store_save_trimmed: the round records of first..last as a trimmed store file at `path` (written to
+        path + ".tmp", then os.replace). A trimmed store is copied value by value; an untrimmed one is converted: each
+        record's decoded Signature under the record's key. patches: {round: bytes | None} replaces or inserts the
+        record of a round inside first..last, None deletes it.
+
+        Records of an untrimmed store that are not canonical hexjson and that no patch covers are decoded here, by
+        beacon_from_hexjson, and written under their KEY (a Round field that differs from the key is not followed); one
+        that does not decode is dropped and listed under "undecodable".
+
+        Returns {"rows", "leaves", "pages", "replaced_or_deleted", "inserted", "unlinked", "undecodable"}. "unlinked":
+        the rounds whose record stored a PreviousSig that the written file's record of round - 1 does not equal (or does
+        not hold): a chained verifier reading the new file sees another previous signature for them than the old record
+        carried. Always empty for a trimmed source. `path` may not be the store's own file."""
+        lib = _lib.load()
+        _refuse_same_file(path, self.path)
+        first = int(first)
+        last = (1 << 64) - 1 if last is None else int(last)
+        patches = dict(patches or {})
+        undecodable = []
+        cap = int(os.path.getsize(self.path)) + 2 * sum(len(v) for v in patches.values() if v is not None) + 64 * int(page_size)
+        ucap = 1024
+        while True:
+            pr, ps, pl, stride = _patch_arrays(patches)
+            image = np.empty(cap, np.uint8)
+            unl = np.zeros(ucap, np.uint64)
+            n, nu = ctypes.c_size_t(0), ctypes.c_size_t(0)
+            stats = (ctypes.c_uint64 * 6)()
+            rc = lib.dh_store_save_trimmed(self._h, first, last, ctypes.c_void_p(pr.ctypes.data), ctypes.c_void_p(ps.ctypes.data),
+                                           stride, ctypes.c_void_p(pl.ctypes.data), len(patches), int(page_size),
+                                           ctypes.c_void_p(image.ctypes.data), cap, ctypes.byref(n),
+                                           ctypes.c_void_p(unl.ctypes.data), ucap, ctypes.byref(nu), stats)
+            if rc == _lib.DH_DEFERRED:  # decided by the host decoder, once
+                todo = [k for k in self.deferred(first, last) if k not in patches]
+                if not todo:
+                    raise RuntimeError("dh_store_save_trimmed keeps deferring records that are patched")
+                for k in todo:
+                    try:
+                        patches[k] = beacon_from_hexjson(self._raw(k)).signature
+                    except DECODE_ERRORS:
+                        patches[k] = None
+                        undecodable.append(k)
+                continue
+            if rc == _lib.DH_EINVAL and (n.value > cap or nu.value > ucap):
+                cap, ucap = max(cap, n.value), max(ucap, nu.value)
+                continue
+            self._raise(rc)
+            break
+        _replace_file(path, image[:n.value])
+        return {"rows": int(stats[0]), "leaves": int(stats[1]), "pages": int(stats[2]), "replaced_or_deleted": int(stats[4]),
+                "inserted": int(stats[5]), "unlinked": [int(x) for x in unl[:nu.value]], "undecodable": undecodable}
+
+
+def _refuse_same_file(path, source):
+    same = os.path.realpath(path) == os.path.realpath(source)
+    if not same and os.path.exists(path):
+        same = os.path.samefile(path, source)
+    if same:
+        raise ValueError("%r is the store's own source file: write to another name and rename" % (path,))
+
+
+def _replace_file(path, image):
+    tmp = str(path) + ".tmp"
+    with open(tmp, "wb") as f:
+        image.tofile(f)
+    os.replace(tmp, path)
+
+
+def _patch_arrays(patches):
+    """(rounds u64[k], sigs u8[k, stride], lens u32[k], stride) of {round: bytes | None}, ascending."""
+    keys = sorted(int(r) for r in patches)
+    stride = max([4] + [len(patches[r]) for r in keys if patches[r] is not None])
+    rounds = np.array(keys, dtype=np.uint64).reshape(-1)
+    sigs = np.zeros((len(keys), stride), np.uint8)
+    lens = np.zeros(len(keys), np.uint32)
+    for i, r in enumerate(keys):
+        v = patches[r]
+        if v is None:
+            lens[i] = _lib.DH_PATCH_DELETE
+        else:
+            lens[i] = len(v)
+            sigs[i, :len(v)] = np.frombuffer(bytes(v), np.uint8)
+    return rounds, sigs, lens, stride
+
+
+def write_trimmed_bolt(path, rounds, sigs, lens=None, page_size=4096):
+    """dh_bolt_write_trimmed_device: a trimmed store file (chain/boltdb/trimmed.go:87-107 of the reference: bucket
+    "beacons", key = round, value = signature) from columns: rounds u64[n] strictly ascending, sigs u8[n, stride],
+    lens u32[n] (default: every value is the full row). numpy arrays are uploaded; torch tensors on the device (rounds
+    int64 carrying the u64 bit pattern, lens int32, as DeviceBoltStore.columns_device returns them) are used in place.
+    Written to path + ".tmp", then os.replace. Returns {"rows", "leaves", "pages"}."""
+    import torch
+    lib = _lib.load()
+    dev = torch.device("cuda")
+
+    def tensor(x, np_dtype, view):
+        if isinstance(x, torch.Tensor):
+            return x.to(dev).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(x, dtype=np_dtype).view(view)).to(dev)
+
+    d_rounds = tensor(rounds, np.uint64, np.int64).reshape(-1)
+    d_sigs = tensor(sigs, np.uint8, np.uint8)
+    n = d_rounds.numel()
+    if d_sigs.dim() != 2 or d_sigs.shape[0] != n or d_sigs.dtype != torch.uint8 or d_rounds.dtype != torch.int64:
+        raise ValueError("rounds int64/uint64 [n] and sigs uint8 [n, stride]")
+    stride = int(d_sigs.shape[1])
+    if lens is None:
+        d_lens = torch.full((n,), stride, dtype=torch.int32, device=dev)
+    else:
+        d_lens = tensor(lens, np.uint32, np.int32).reshape(-1)
+        if d_lens.numel() != n or d_lens.dtype != torch.int32:
+            raise ValueError("lens int32/uint32 [n]")
+    torch.cuda.synchronize()
+    size = ctypes.c_size_t(0)
+    stats = (ctypes.c_uint64 * 3)()
+    args = (d_rounds.data_ptr() or None, d_sigs.data_ptr() or None, stride, d_lens.data_ptr() or None, n, int(page_size))
+    rc = lib.dh_bolt_write_trimmed_device(*args, None, 0, ctypes.byref(size), stats, None)
+    if rc != _lib.DH_EINVAL or not size.value:  # DH_EINVAL with the size needed
+        DeviceBoltStore._raise(rc)
+    image = np.empty(size.value, np.uint8)
+    DeviceBoltStore._raise(lib.dh_bolt_write_trimmed_device(*args, ctypes.c_void_p(image.ctypes.data), image.size,
+                                                            ctypes.byref(size), stats, None))
+    _replace_file(path, image[:size.value])
+    return {"rows": int(stats[0]), "leaves": int(stats[1]), "pages": int(stats[2])}
 
 
 class BoltUntrimmedStore(_BoltStoreBase):

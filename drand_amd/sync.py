@@ -121,6 +121,60 @@ def check_past_beacons(store, scheme, pubkey, up_to, cb=None, window=1 << 20, se
     return faulty
 
 
+def correct_store_file(src, dst, scheme, pubkey, fetch, up_to=None, fmt="auto"):
+    """CheckPastBeacons followed by CorrectPastBeacons (chain/beacon/sync_manager.go:170-268 of the reference), offline,
+    from the store file `src` to a new trimmed store file `dst` (the daemon is stopped, `dst` is renamed
+    over `src` by the caller when it is satisfied):
+      1. check_past over `src` on the device: the faulty rounds up to `up_to` (default: the last stored round);
+      2. fetch(round) -> signature bytes | None, once per faulty round (the caller's network code);
+      3. ONE scheme.verify_beacons call over the fetched records; for the chained scheme the previous signature of
+         round r is the fetched signature of r - 1 when there is one, else the stored one;
+      4. only the records that verify become patches of DeviceBoltStore.save_trimmed(dst);
+      5. `dst` is reopened and checked again.
+    Returns (faulty_before, faulty_after, unlinked): the two checks' lists and save_trimmed's unlinked rounds.
+
+    Deviation from the reference: CorrectPastBeacons re-syncs the faulty rounds through the sync manager, where every
+    streamed packet carries its own PreviousSig and is verified against it, and later packets can build on earlier
+    ones as they are stored. This is one conservative pass: a fetched record is judged against its fetched or stored
+    neighbour exactly once, a record that does not verify in that pass is not written, and nothing is retried; rounds
+    left faulty are in faulty_after for the caller to fetch again."""
+    from . import store as _store
+    with _store.DeviceBoltStore(src, scheme.chained, fmt=fmt) as st:
+        rng = st.rounds_range()
+        if rng is None:
+            raise NoBeaconStored("empty store")
+        if up_to is None:
+            up_to = rng[1]
+        faulty_before = st.check_past(scheme, pubkey, up_to)
+        fetched = {}
+        for r in faulty_before:
+            sig = fetch(r)
+            if sig is not None:
+                fetched[int(r)] = bytes(sig)
+        cand = [r for r in sorted(fetched) if len(fetched[r]) == scheme.sig_len]
+        patches = {}
+        if cand:
+            prevs = None
+            if scheme.chained:
+                prevs = []
+                for r in cand:
+                    if r - 1 in fetched:
+                        prevs.append(fetched[r - 1])
+                        continue
+                    try:
+                        prevs.append(st.stored_signature(r - 1))
+                    except (NoBeaconStored,) + _store.DECODE_ERRORS:
+                        prevs.append(b"")  # nothing to verify against: the record is not written
+            rounds = np.array(cand, dtype=np.uint64)
+            sigs = np.frombuffer(b"".join(fetched[r] for r in cand), np.uint8).reshape(len(cand), scheme.sig_len).copy()
+            ok, _ = scheme.verify_beacons(pubkey, rounds, sigs, prevs, want_randomness=False)
+            patches = {r: fetched[r] for r, v in zip(cand, ok) if v}
+        res = st.save_trimmed(dst, patches=patches)
+    with _store.DeviceBoltStore(dst, scheme.chained, fmt="trimmed") as out:
+        faulty_after = out.check_past(scheme, pubkey, up_to)
+    return faulty_before, faulty_after, res["unlinked"]
+
+
 class WrongBeaconID(Exception):
     pass
 

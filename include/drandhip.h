@@ -390,6 +390,55 @@ int dh_store_beacons_device(dh_store* store, uint64_t first, uint64_t last, size
 int dh_store_deferred(dh_store* store, uint64_t first, uint64_t last, uint64_t* out, size_t cap, size_t* n_out);
 
 /*
+ * Writing a trimmed store file from columns in device memory: the image of the file that
+ * chain/boltdb/trimmed.go:87-107 fills (bucket "beacons", key = round as 8 bytes big-endian, value = the raw
+ * signature, leaves packed full: bucket.FillPercent = 1.0). This is a FILE WRITER, not bbolt: no transactions, no
+ * update of a live store, no freelist reuse. It serves the two things the reference leaves to a serial Put loop:
+ * converting a legacy store, whose format shouldUseTrimmedBolt (chain/boltdb/store.go:82-110) keeps for ever, and
+ * acting on CheckPastBeacons the way CorrectPastBeacons does (chain/beacon/sync_manager.go:237-268). The layout is
+ * fixed: pages 0 / 1 meta (txid 3 / 2), 2 an empty freelist, 3 the root bucket's leaf, the bucket's leaves from page 4
+ * (a record needs 16 + 8 + vsize bytes, a leaf closes when 16 + the sum would pass the page size, a record that alone
+ * passes it gets overflow pages), then branch levels of (page_size - 16) / 24 children up to one root.
+ *
+ * dh_bolt_write_trimmed_device: the primitive. d_rounds / d_rows / d_lens: n rows in the layout
+ * dh_store_columns_device and dh_store_beacons_device produce (strictly ascending rounds, value i = d_lens[i] bytes at
+ * d_rows + i*row_stride, d_lens[i] <= row_stride; a violation is DH_EINVAL, found on the device before anything is
+ * written). page_size: a power of two from 256 to 65536, else DH_EINVAL. image_out: HOST memory of `cap` bytes;
+ * *len_out = the size of the image, a multiple of page_size; cap too small: DH_EINVAL with *len_out set and nothing
+ * written. n = 0: DH_ENOBEACON (no empty store is written). n above 16M rows: DH_EINVAL. An image above
+ * DRANDHIP_STORE_MAX_BYTES or a failed allocation: DH_ENOMEM. stats_out (nullable) = {rows, leaves, pages}. Work queued
+ * on hip_stream is waited for first; the call returns when the image is complete.
+ */
+#define DH_PATCH_DELETE 0xFFFFFFFFu
+int dh_bolt_write_trimmed_device(const uint64_t* d_rounds, const uint8_t* d_rows, size_t row_stride, const uint32_t* d_lens,
+                                 size_t n, uint32_t page_size, uint8_t* image_out, size_t cap, size_t* len_out,
+                                 uint64_t stats_out[3], void* hip_stream);
+/*
+ * dh_store_save_trimmed: the round records of first..last of an open store, of either format, as a trimmed file image.
+ * A trimmed handle copies the values as stored, of any length (a compacted or ranged copy); an untrimmed handle writes
+ * each canonical record's decoded Signature (chain/boltdb/store.go:143-168 -> trimmed.go:87-107). Elements that are not
+ * round records (keys not 8 bytes, nested buckets) are not copied.
+ * Patches (CorrectPastBeacons' Put of the refetched rounds, sync_manager.go:237-268): n_patch <= 2^20 rounds, strictly
+ * ascending and inside [first, last], else DH_EINVAL; patch i replaces the record of its round or inserts it with the
+ * patch_lens[i] <= patch_stride bytes at patch_sigs + i*patch_stride; patch_lens[i] == DH_PATCH_DELETE drops the record.
+ * A deferred record in the range that no patch covers: DH_DEFERRED with *len_out = 0 and nothing written; list them
+ * with dh_store_deferred, decode them, pass them as patches (or delete them) and call again.
+ * The trimmed reader takes the previous signature of round r from the value of round r - 1 (trimmed.go:156-193), while
+ * an untrimmed record stored its own. A row taken from a canonical record is UNLINKED when its decoded PreviousSig has
+ * nonzero length and the output holds no row for round - 1 or that row's value differs from it in length or bytes:
+ * exactly the rounds for which the written file hands a chained verifier another previous signature than the record
+ * stored. unlinked_out: those rounds, ascending; more than unlinked_cap: DH_EINVAL with *n_unlinked_out = the number
+ * and *len_out = the image size, nothing written. Always empty for a trimmed handle.
+ * image_out / cap / len_out / page_size and the limits as above (rows + patches below 16M). stats_out (nullable) =
+ * {rows written, leaves, pages, unlinked, patches that replaced or deleted a record, patches that inserted one}.
+ * dh_profile stages: store_save_merge, store_save_plan, store_save_pack, store_save_download.
+ */
+int dh_store_save_trimmed(dh_store* store, uint64_t first, uint64_t last, const uint64_t* patch_rounds, const uint8_t* patch_sigs,
+                          size_t patch_stride, const uint32_t* patch_lens, size_t n_patch, uint32_t page_size,
+                          uint8_t* image_out, size_t cap, size_t* len_out, uint64_t* unlinked_out, size_t unlinked_cap,
+                          size_t* n_unlinked_out, uint64_t stats_out[6]);
+
+/*
  * Synthetic-chain utilities (test fixtures and benchmark inputs; not part of the verification path):
  * sign n beacons with a 32-byte big-endian secret scalar, sig_i = [sk] H(DigestBeacon(round_i, prev_i)),
  * the mock chain pattern of client/test/result/mock/result.go:84-127; and the matching group key [sk] g.
