@@ -82,6 +82,13 @@ SIGNATURES = {
     "dh_bolt_write_trimmed_device": (_c.c_int, [_P, _P, _c.c_size_t, _P, _c.c_size_t, _c.c_uint32, _P, _c.c_size_t, _P, _P, _P]),
     "dh_store_save_trimmed": (_c.c_int, [_P, _c.c_uint64, _c.c_uint64, _P, _P, _c.c_size_t, _P, _c.c_size_t, _c.c_uint32, _P,
                                          _c.c_size_t, _P, _P, _c.c_size_t, _P, _P]),
+    "dh_bolt_writer_open": (_c.c_int, [_c.c_uint32, _c.POINTER(_P)]),
+    "dh_bolt_writer_append_device": (_c.c_int, [_P, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t, _P, _P, _P, _P]),
+    "dh_bolt_writer_finish": (_c.c_int, [_P, _P, _c.c_size_t, _P, _P, _P, _P]),
+    "dh_bolt_writer_close": (None, [_P]),
+    "dh_store_save_trimmed_append": (_c.c_int, [_P, _P, _c.c_uint64, _c.c_uint64, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
+                                                _c.c_size_t, _P, _P, _P, _c.c_size_t, _P, _P]),
+    "dh_store_split": (_c.c_int, [_P, _c.c_uint64, _c.c_uint64, _c.c_size_t, _P, _c.c_size_t, _P]),
     "dh_profile": (_c.c_int, [_c.c_int]),
     "dh_profile_read": (_c.c_int, [_c.c_char_p, _c.c_size_t]),
     "dh_last_error_string": (_c.c_char_p, []),

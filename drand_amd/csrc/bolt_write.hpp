@@ -93,6 +93,39 @@ BOLT_HD uint32_t plan_leaf(const uint32_t* sums, uint64_t n, uint64_t s, uint32_
   return k;
 }
 
+// The same leaf when rows [0, m) are a window of a longer list: the rows taken when the leaf is
+// certainly closed, 0 while it is open. Closed means a following record is known not to fit: one follows in the window
+// and did not fit, or no record of at least 24 bytes fits any more (a record with 16 + need > P is such a leaf of its
+// own, as is a leaf filled to the last 23 bytes), or `final`: nothing follows. An open leaf therefore holds at most
+// P - 24 bytes, i.e. fewer than MAX_LEAF_RECS rows: the bound of what a writer carries to its next window.
+BOLT_HD uint32_t plan_leaf_window(const uint32_t* sums, uint64_t m, uint64_t s, uint32_t P, uint64_t page, bool final, leaf_desc* out) {
+  const uint32_t k = plan_leaf(sums, m, s, P, page, out);
+  if (final || s + k < m) return k;
+  const uint64_t size = 16 + (uint64_t)(uint32_t)(sums[s + k] - sums[s]);  // exact: k > 1 keeps it within P, k = 1 below 2^32
+  return size + 24 > P ? k : 0;
+}
+
+struct window_plan {
+  uint64_t leaves;     // leaves closed by this window
+  uint64_t open_row;   // first row of the open leaf (m when none is open): rows [open_row, m) are carried
+  uint64_t next_page;  // the page of the next leaf
+};
+// The windowed leaf plan over rows [0, m) = (carried rows || new rows), the next leaf going to `page`. The closed
+// leaves are written to out[0, cap) in order; those beyond cap are counted only, so a call with cap 0 sizes.
+BOLT_HD window_plan plan_window(const uint32_t* sums, uint64_t m, uint32_t P, uint64_t page, bool final, leaf_desc* out, uint64_t cap) {
+  window_plan w{0, 0, page};
+  while (w.open_row < m) {
+    leaf_desc L;
+    const uint32_t k = plan_leaf_window(sums, m, w.open_row, P, w.next_page, final, &L);
+    if (!k) break;
+    if (w.leaves < cap) out[w.leaves] = L;
+    w.leaves++;
+    w.open_row += k;
+    w.next_page += L.span;
+  }
+  return w;
+}
+
 // ---- a leaf's bytes
 
 // the columns the records come from
@@ -101,14 +134,30 @@ struct cols {
   const uint8_t* rows;
   uint64_t stride;
   const uint32_t* lens;
+  BOLT_HD uint64_t round(uint64_t i) const { return rounds[i]; }
+  BOLT_HD uint32_t len(uint64_t i) const { return lens[i]; }
+  BOLT_HD uint8_t byte(uint64_t i, uint32_t o) const { return rows[i * stride + o]; }
+};
+
+// Two row segments read as one list: rows below n_carry are the writer's carried rows, row i from
+// n_carry on is row i - n_carry of the caller's columns; each segment has its own stride.
+struct cols2 {
+  cols carry, fresh;
+  uint64_t n_carry;
+  BOLT_HD uint64_t round(uint64_t i) const { return i < n_carry ? carry.rounds[i] : fresh.rounds[i - n_carry]; }
+  BOLT_HD uint32_t len(uint64_t i) const { return i < n_carry ? carry.lens[i] : fresh.lens[i - n_carry]; }
+  BOLT_HD uint8_t byte(uint64_t i, uint32_t o) const {
+    return i < n_carry ? carry.rows[i * carry.stride + o] : fresh.rows[(i - n_carry) * fresh.stride + o];
+  }
 };
 
 // Data offsets of a MIXED leaf's records behind its element array: offs[i] for record i, offs[n] the end (n + 1 words).
-BOLT_HD void leaf_offsets(const leaf_desc& L, const cols& c, uint32_t* offs) {
+template <class C>
+BOLT_HD void leaf_offsets(const leaf_desc& L, const C& c, uint32_t* offs) {
   uint32_t o = 0;
   for (uint32_t i = 0; i < L.n; i++) {
     offs[i] = o;
-    o += 8 + c.lens[L.row0 + i];
+    o += 8 + c.len((uint64_t)L.row0 + i);
   }
   offs[L.n] = o;
 }
@@ -121,7 +170,8 @@ BOLT_HD uint32_t data_off(const leaf_desc& L, const uint32_t* offs, uint32_t i) 
 // Dword w (little-endian) of the leaf's extent of span * P bytes: the page header {id, flags 0x02, count, overflow},
 // element i {flags 0, pos relative to the element, ksize 8, vsize}, then per record key and value, then zeros. The
 // element array ends on a dword boundary, so a dword lies in one region; inside the data it may cross records.
-BOLT_HD uint32_t leaf_dword(const leaf_desc& L, const cols& c, const uint32_t* offs, uint32_t w) {
+template <class C>
+BOLT_HD uint32_t leaf_dword(const leaf_desc& L, const C& c, const uint32_t* offs, uint32_t w) {
   if (w < 4) {
     if (w == 0) return (uint32_t)L.page;
     if (w == 1) return (uint32_t)(L.page >> 32);
@@ -153,7 +203,7 @@ BOLT_HD uint32_t leaf_dword(const leaf_desc& L, const cols& c, const uint32_t* o
     while (d + j >= next) next = data_off(L, offs, ++r + 1);  // a record is at least its 8-byte key
     const uint32_t o = d + j - data_off(L, offs, r);
     const uint64_t row = (uint64_t)L.row0 + r;
-    const uint32_t b = o < 8 ? (uint32_t)(c.rounds[row] >> (8 * (7 - o))) & 0xff : c.rows[row * c.stride + (o - 8)];
+    const uint32_t b = o < 8 ? (uint32_t)(c.round(row) >> (8 * (7 - o))) & 0xff : c.byte(row, o - 8);
     word |= b << (8 * j);
   }
   return word;
@@ -219,28 +269,35 @@ BOLT_HD uint64_t branch_pages(uint64_t leaves, uint32_t P) {
   return total;
 }
 
-// The branch levels, pages 0, 1, 2 and 3. `img` is the whole image (pages * P bytes) whose leaf pages are in place;
-// keys / pgids hold the first key and the page of every leaf on entry (`leaves` >= 1 entries) and are overwritten level
-// by level. leaf_end is the page after the last leaf page. Returns the bucket's root page.
-BOLT_HD uint64_t finish_image(uint8_t* img, uint32_t P, uint64_t pages, uint64_t leaf_end, uint64_t* keys, uint64_t* pgids,
-                              uint64_t leaves) {
+// The branch levels, pages 0, 1, 2 and 3 of a file whose leaf pages are not in memory. keys / pgids hold the first key
+// and the page of every leaf on entry (`leaves` >= 1 entries) and are overwritten level by level. leaf_end is the page
+// after the last leaf page; `tail` starts there and takes the branch_pages(leaves, P) branch pages, whose page ids stay
+// absolute; `head` takes pages 0-3 (4 * P bytes). Returns the bucket's root page.
+BOLT_HD uint64_t finish_tail(uint8_t* tail, uint8_t* head, uint32_t P, uint64_t pages, uint64_t leaf_end, uint64_t* keys,
+                             uint64_t* pgids, uint64_t leaves) {
   uint64_t nxt = leaf_end, level = leaves;
   const uint32_t fan = branch_fan(P);
   while (level > 1) {
     uint64_t up = 0;
     for (uint64_t i = 0; i < level; i += fan, up++) {
       const uint32_t k = (uint32_t)(level - i < fan ? level - i : fan);
-      branch_page(img + nxt * P, P, nxt, keys + i, pgids + i, k);
+      branch_page(tail + (nxt - leaf_end) * P, P, nxt, keys + i, pgids + i, k);
       keys[up] = keys[i];  // up <= i: the entries read later lie further on
       pgids[up] = nxt++;
     }
     level = up;
   }
-  meta_page(img, P, 0, pages, 3);
-  meta_page(img + P, P, 1, pages, 2);
-  freelist_page(img + 2 * (uint64_t)P, P);
-  root_leaf_page(img + 3 * (uint64_t)P, P, pgids[0]);
+  meta_page(head, P, 0, pages, 3);
+  meta_page(head + P, P, 1, pages, 2);
+  freelist_page(head + 2 * (uint64_t)P, P);
+  root_leaf_page(head + 3 * (uint64_t)P, P, pgids[0]);
   return pgids[0];
+}
+
+// The same for a whole image (pages * P bytes) whose leaf pages are in place.
+BOLT_HD uint64_t finish_image(uint8_t* img, uint32_t P, uint64_t pages, uint64_t leaf_end, uint64_t* keys, uint64_t* pgids,
+                              uint64_t leaves) {
+  return finish_tail(img + leaf_end * P, img, P, pages, leaf_end, keys, pgids, leaves);
 }
 
 }  // namespace boltw

@@ -2931,14 +2931,56 @@ struct prof_wall {  // host wall time of one store stage (each ends in a stream 
   }
 };
 
-// device scratch of one trimmed-store write
-struct write_ws {
+// The windowed writer: rows arrive in windows; the leaves a window closes are packed and emitted, the
+// open leaf's rows are carried to the next window in one of two carry sets (the pack and the carry-out of a window read
+// set `cur` and write the other), the branch levels and pages 0-3 are written at the end.
+struct bw_plan {  // what decides the layout of the rows to come; the host's 16 bytes per leaf are in bw_state
+  std::vector<uint32_t> carry_need;  // record sizes of the open leaf's rows: at most P - 40 bytes, below MAX_LEAF_RECS rows
+  uint64_t next_page = dh::boltw::FIRST_LEAF_PAGE, leaves = 0, rows = 0;
+};
+struct bw_window {  // one window's plan
+  std::vector<uint32_t> sums;  // exclusive sums over (carried rows || new rows)
+  std::vector<dh::boltw::leaf_desc> leaves;
+  std::vector<uint64_t> keys;  // the closed leaves' first keys, downloaded
+  uint64_t m = 0, open_row = 0, next_page = 0;
+};
+struct bw_state {
+  uint32_t P = 0;
+  bw_plan plan;
+  bool has_last = false, finished = false;
+  uint64_t call_base = 0;  // a one-shot call: the bytes of its image in front of the window's run (DRANDHIP_STORE_MAX_BYTES)
+  int cur = 0;
+  size_t carry_stride = 4;
+  struct carry_set {
+    dbuf rounds, rows, lens, last;  // last: {u64 round, u64 length, value bytes} of the last row appended
+  } set[2];
+  static_assert(dh::boltw::MAX_LEAF_RECS * 24 + 16 >= 65536 - 24, "an open leaf (at most P - 24 bytes) stays below MAX_LEAF_RECS rows");
   dbuf need, sums, scan_tmp, err, leaves, image, keys;
-  // dh_store_save_trimmed: the uploaded patches, the merge's slots and the merged columns
+  std::vector<uint64_t> h_keys, h_pgids;  // first key and page of every closed leaf
+  bw_window win;
+  void reset(uint32_t page_size) {
+    P = page_size;
+    plan = bw_plan();
+    has_last = finished = false;
+    call_base = 0;
+    h_keys.clear();
+    h_pgids.clear();
+  }
+  void release() {
+    for (dbuf* b : {&need, &sums, &scan_tmp, &err, &leaves, &image, &keys, &set[0].rounds, &set[0].rows, &set[0].lens, &set[0].last,
+                    &set[1].rounds, &set[1].rows, &set[1].lens, &set[1].last})
+      b->release();
+  }
+};
+
+// device scratch of dh_store_save_trimmed: the uploaded patches, the merge's slots and the merged columns
+struct write_ws {
+  bw_state bw;
+  dbuf scan_tmp, err, pred[2];  // pred: the sizing pass's last merged row (the layout of carry_out.last)
   dbuf p_rounds, p_rows, p_lens, flag, lb, pos, hit, o_rounds, o_rows, o_lens, o_src, unl;
   void release() {
-    for (dbuf* b : {&need, &sums, &scan_tmp, &err, &leaves, &image, &keys, &p_rounds, &p_rows, &p_lens, &flag, &lb, &pos, &hit,
-                    &o_rounds, &o_rows, &o_lens, &o_src, &unl})
+    bw.release();
+    for (dbuf* b : {&scan_tmp, &err, &pred[0], &pred[1], &p_rounds, &p_rows, &p_lens, &flag, &lb, &pos, &hit, &o_rounds, &o_rows, &o_lens, &o_src, &unl})
       b->release();
   }
 };
@@ -2972,8 +3014,22 @@ struct dh_store {
     dead = true;
   }
 };
+struct dh_bolt_writer {  // locking and lifetime as dh_store
+  std::mutex mu;
+  std::atomic<bool> retire{false};
+  bool dead = false;
+  hipStream_t st = nullptr;
+  bw_state bw;
+  void release() {
+    bw.release();
+    if (st) (void)hipStreamDestroy(st);
+    st = nullptr;
+    dead = true;
+  }
+};
 static std::mutex g_stores_mu;
 static std::vector<dh_store*> g_stores;
+static std::vector<dh_bolt_writer*> g_writers;  // under g_stores_mu
 
 // dh_shutdown: idle handles lose their device memory now, a handle inside a call when that call ends
 static void stores_shutdown() {
@@ -2984,6 +3040,14 @@ static void stores_shutdown() {
       s->mu.unlock();
     } else {
       s->retire = true;
+    }
+  }
+  for (dh_bolt_writer* w : g_writers) {
+    if (w->mu.try_lock()) {
+      w->release();
+      w->mu.unlock();
+    } else {
+      w->retire = true;
     }
   }
 }
@@ -3561,71 +3625,214 @@ int dh_store_deferred(dh_store* s, uint64_t first, uint64_t last, uint64_t* out,
 // device packs the leaf pages (k_bolt_write.hip), the host plans them from the scanned record sizes and writes the
 // branch levels and pages 0-3.
 
-// Entered with the device set. With cap too small (cap 0 sizes only): DH_EINVAL, *len_out set, nothing written.
-static int bolt_write_core(hipStream_t st, write_ws& ws, const uint64_t* d_rounds, const uint8_t* d_rows, size_t stride,
+static size_t write_window_rows() {  // DRANDHIP_STORE_WRITE_WINDOW, read at every call; default: the scan's limit
+  const char* e = getenv("DRANDHIP_STORE_WRITE_WINDOW");
+  const long long v = e ? atoll(e) : 0;
+  const size_t lim = (size_t)4096 * 4096 - 2;
+  return v >= 1 && (size_t)v < lim ? (size_t)v : lim;
+}
+
+// One window's plan against `pl`, which is not changed: the record sizes of the n new rows on the device, their scan,
+// and the host walk over (carried rows || new rows). `last` (device, nullable): the round the first new row must pass.
+static int bw_plan_window(bw_state& w, hipStream_t st, const bw_plan& pl, const dh::boltw::cols& fresh, size_t n, const uint64_t* last,
+                          bool final, bw_window& out) {
+  using namespace dh::boltw;
+  if (n + 2 > (size_t)4096 * 4096) return fail(DH_EINVAL, "window of %zu rows: at most 16M rows per window", n);
+  const size_t nc = pl.carry_need.size();
+  out.m = nc + n;
+  out.sums.resize(out.m + 1);
+  uint32_t* sums = out.sums.data();
+  sums[nc] = 0;
+  if (n) {
+    uint32_t err_word = 0;
+    HIP_TRY(w.need.ensure(n * 4));
+    HIP_TRY(w.sums.ensure((n + 1) * 4));
+    HIP_TRY(w.scan_tmp.ensure((n / 4096 + 2) * 4));
+    HIP_TRY(w.err.ensure(4));
+    HIP_TRY(hipMemsetAsync(w.err.p, 0, 4, st));
+    HIP_TRY(dh::launch_bolt_need(fresh, n, last, w.need.as<uint32_t>(), w.err.as<uint32_t>(), st));
+    HIP_TRY(dh::launch_scan(w.need.as<uint32_t>(), n, w.sums.as<uint32_t>(), w.scan_tmp.as<uint32_t>(), st));
+    HIP_TRY(hipMemcpyAsync(sums + nc, w.sums.p, (n + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&err_word, w.err.p, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (err_word)
+      return fail(DH_EINVAL, "rounds not strictly ascending, or a value longer than the row stride %llu", (unsigned long long)fresh.stride);
+  }
+  if (nc) {  // the carried rows' sizes in front (modulo 2^32, as the scan leaves the rest)
+    uint32_t base = 0;
+    for (size_t i = 0; i < nc; i++) {
+      sums[i] = base;
+      base += pl.carry_need[i];
+    }
+    for (size_t i = nc; i <= out.m; i++) sums[i] += base;
+  }
+  // the greedy leaf boundaries: plan_window's host walk over the sums (8 bytes a row with the copy, well below the
+  // pack's time), into the room the last window's plan left; walked again only when this one closes more leaves
+  out.leaves.resize(out.leaves.capacity());
+  window_plan wp = plan_window(sums, out.m, w.P, pl.next_page, final, out.leaves.data(), out.leaves.size());
+  if (wp.leaves > out.leaves.size()) {
+    out.leaves.resize(wp.leaves);
+    wp = plan_window(sums, out.m, w.P, pl.next_page, final, out.leaves.data(), out.leaves.size());
+  }
+  out.leaves.resize(wp.leaves);
+  out.open_row = wp.open_row;
+  out.next_page = wp.next_page;
+  return DH_OK;
+}
+
+// the plan state behind a planned window of n new rows
+static void bw_advance(bw_plan& pl, const bw_window& win, size_t n) {
+  std::vector<uint32_t> need(win.m - win.open_row);
+  for (uint64_t i = win.open_row; i < win.m; i++) need[i - win.open_row] = win.sums[i + 1] - win.sums[i];
+  pl.carry_need.swap(need);
+  pl.next_page = win.next_page;
+  pl.leaves += win.leaves.size();
+  pl.rows += n;
+}
+
+// One window into the writer: the closed leaves' pages to out[0, *len_out), which belong at *file_off_out. With
+// `final` the open leaf is closed too, the branch pages follow the run in `out`, pages 0-3 go to `head` and st3 is the
+// file's {rows, leaves, pages}; otherwise st3 is this window's {rows taken, leaves closed, pages emitted}. On every
+// failure the writer is as before the call; cap too small (cap 0 sizes): DH_EINVAL with *len_out set.
+static int bw_append(bw_state& w, hipStream_t st, const dh::boltw::cols& fresh, size_t n, bool final, uint8_t* out, size_t cap,
+                     size_t* len_out, uint64_t* file_off_out, uint8_t* head, uint64_t st3[3], const char* const stage[3]) {
+  using namespace dh::boltw;
+  *len_out = 0;
+  const uint32_t P = w.P;
+  if (file_off_out) *file_off_out = w.plan.next_page * P;
+  if (st3) st3[0] = st3[1] = st3[2] = 0;
+  if (w.finished) return fail(DH_EINVAL, "the writer is finished");
+  if (final && !(w.plan.rows + n)) return fail(DH_ENOBEACON, "no beacon to write: an empty store is not written");
+  if (!n && !final) return DH_OK;
+  bw_window& win = w.win;
+  bw_state::carry_set& old = w.set[w.cur];
+  bw_state::carry_set& nxt = w.set[w.cur ^ 1];
+  const size_t nc = w.plan.carry_need.size();
+  {
+    prof_wall p(stage[0]);
+    int rc = bw_plan_window(w, st, w.plan, fresh, n, w.has_last ? old.last.as<uint64_t>() : nullptr, final, win);
+    if (rc) return rc;
+  }
+  const size_t nl = win.leaves.size();
+  const uint64_t run_bytes = (win.next_page - w.plan.next_page) * P;
+  const uint64_t all_leaves = w.plan.leaves + nl;
+  const uint64_t pages = win.next_page + (final ? branch_pages(all_leaves, P) : 0);
+  const uint64_t bytes = (pages - w.plan.next_page) * P;
+  *len_out = (size_t)bytes;
+  if (st3) {
+    st3[0] = final ? w.plan.rows + n : n;
+    st3[1] = final ? all_leaves : nl;
+    st3[2] = final ? pages : win.next_page - w.plan.next_page;
+  }
+  if (bytes + w.call_base > store_max_bytes())  // what the call emits: a one-shot call's image from byte 0
+    return fail(DH_ENOMEM, "store image of %llu bytes exceeds DRANDHIP_STORE_MAX_BYTES (%zu)", (unsigned long long)(bytes + w.call_base),
+                store_max_bytes());
+  if (cap < bytes || (bytes && !out) || (final && !head))
+    return fail(DH_EINVAL, "store image of %llu bytes, room for %zu", (unsigned long long)bytes, cap);
+  // a segment without rows still gets the other segment's (readable) addresses, never null ones: a wave-uniform address
+  // is read by scalar loads, which no lane mask holds back (k_bolt_write.hip, k_bolt_unlinked)
+  const cols carried{old.rounds.as<uint64_t>(), old.rows.as<uint8_t>(), w.carry_stride, old.lens.as<uint32_t>()};
+  const cols2 c{nc ? carried : fresh, n ? fresh : carried, nc};
+  const uint64_t n_open = win.m - win.open_row;
+  uint32_t longest = 0;
+  for (uint64_t i = win.open_row; i < win.m; i++) longest = std::max(longest, win.sums[i + 1] - win.sums[i] - 24);
+  const size_t nxt_stride = std::max<size_t>(4, ((size_t)longest + 3) & ~(size_t)3);
+  {
+    prof_wall p(stage[1]);
+    HIP_TRY(w.leaves.ensure(nl * sizeof(leaf_desc)));
+    HIP_TRY(w.image.ensure(run_bytes));
+    HIP_TRY(w.keys.ensure(nl * 8));
+    if (nl) HIP_TRY(hipMemcpyAsync(w.leaves.p, win.leaves.data(), nl * sizeof(leaf_desc), hipMemcpyHostToDevice, st));
+    timed_launches tl(st);
+    HIP_TRY(tl.run("k_bolt_pack", [&] {
+      return dh::launch_bolt_pack(w.leaves.p, nl, c, P, w.plan.next_page, w.image.as<uint8_t>(), w.keys.as<uint64_t>(), st);
+    }));
+    if (n) {  // the open leaf's rows and the last row appended, into the other carry set
+      const uint32_t last_len = win.sums[win.m] - win.sums[win.m - 1] - 24;
+      const size_t last_stride = std::max<size_t>(4, ((size_t)last_len + 3) & ~(size_t)3);
+      HIP_TRY(nxt.rounds.ensure(n_open * 8));
+      HIP_TRY(nxt.lens.ensure(n_open * 4));
+      HIP_TRY(nxt.rows.ensure(n_open * nxt_stride));
+      HIP_TRY(nxt.last.ensure(16 + last_stride));
+      const dh::carry_out o{nxt.rounds.as<uint64_t>(), nxt.lens.as<uint32_t>(), nxt.rows.as<uint8_t>(), (uint32_t)nxt_stride,
+                            nxt.last.as<uint64_t>(), (uint32_t)last_stride};
+      HIP_TRY(tl.run("k_bolt_carry", [&] { return dh::launch_bolt_carry(c, win.open_row, n_open, win.m - 1, o, st); }));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  {
+    prof_wall p(stage[2]);
+    win.keys.resize(nl);
+    if (run_bytes) HIP_TRY(hipMemcpyAsync(out, w.image.p, run_bytes, hipMemcpyDeviceToHost, st));
+    if (nl) HIP_TRY(hipMemcpyAsync(win.keys.data(), w.keys.p, nl * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  // committed: nothing below fails
+  w.h_keys.insert(w.h_keys.end(), win.keys.begin(), win.keys.end());
+  for (size_t i = 0; i < nl; i++) w.h_pgids.push_back(win.leaves[i].page);
+  bw_advance(w.plan, win, n);
+  if (n) {
+    w.cur ^= 1;
+    w.carry_stride = nxt_stride;
+    w.has_last = true;
+  }
+  if (final) {
+    finish_tail(out + run_bytes, head, P, pages, win.next_page, w.h_keys.data(), w.h_pgids.data(), all_leaves);
+    w.finished = true;
+  }
+  return DH_OK;
+}
+
+// The one-shot image over n rows in device memory, as a loop over the writer: windows of DRANDHIP_STORE_WRITE_WINDOW
+// rows, the last of them final. Entered with the device set. With cap too small (cap 0 sizes only): DH_EINVAL,
+// *len_out set, nothing written; more than one window is sized by a planning pass of its own first.
+static int bolt_write_core(hipStream_t st, bw_state& w, const uint64_t* d_rounds, const uint8_t* d_rows, size_t stride,
                            const uint32_t* d_lens, size_t n, uint32_t P, uint8_t* image_out, size_t cap, size_t* len_out,
-                           uint64_t stats[3], const char* const stage[3]) {
+                           uint64_t stats[3], const char* const stage[4]) {
   using namespace dh::boltw;
   *len_out = 0;
   if (!n) return fail(DH_ENOBEACON, "no beacon to write: an empty store is not written");
-  if (n + 2 > (size_t)4096 * 4096) return fail(DH_EINVAL, "%zu rows: at most 16M rows per call", n);
-  std::vector<leaf_desc> leaves;
-  uint64_t leaf_end = FIRST_LEAF_PAGE, pages = 0;
-  {
+  const size_t W = write_window_rows();
+  auto cut = [&](size_t off) {
+    return cols{d_rounds + off, d_rows ? d_rows + off * stride : nullptr, (uint64_t)stride, d_lens + off};
+  };
+  w.reset(P);
+  if (n > W) {  // the whole image's size, before a byte is written
     prof_wall p(stage[0]);
-    std::vector<uint32_t> sums(n + 1);
-    uint32_t err_word = 0;
-    HIP_TRY(ws.need.ensure(n * 4));
-    HIP_TRY(ws.sums.ensure((n + 1) * 4));
-    HIP_TRY(ws.scan_tmp.ensure((n / 4096 + 2) * 4));
-    HIP_TRY(ws.err.ensure(4));
-    HIP_TRY(hipMemsetAsync(ws.err.p, 0, 4, st));
-    HIP_TRY(dh::launch_bolt_need(d_rounds, d_lens, n, stride, ws.need.as<uint32_t>(), ws.err.as<uint32_t>(), st));
-    HIP_TRY(dh::launch_scan(ws.need.as<uint32_t>(), n, ws.sums.as<uint32_t>(), ws.scan_tmp.as<uint32_t>(), st));
-    HIP_TRY(hipMemcpyAsync(sums.data(), ws.sums.p, (n + 1) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(&err_word, ws.err.p, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (err_word) return fail(DH_EINVAL, "rounds not strictly ascending, or a value longer than the row stride %zu", stride);
-    // the greedy leaf boundaries: a host walk over the sums (8 bytes a row with the copy, well below the pack's time)
-    for (uint64_t s = 0; s < n;) {
-      leaf_desc L;
-      s += plan_leaf(sums.data(), n, s, P, leaf_end, &L);
-      leaf_end += L.span;
-      leaves.push_back(L);
+    bw_plan shadow;
+    for (size_t off = 0; off < n; off += W) {
+      const size_t k = std::min(W, n - off);
+      int rc = bw_plan_window(w, st, shadow, cut(off), k, off ? d_rounds + off - 1 : nullptr, off + k == n, w.win);
+      if (rc) return rc;
+      bw_advance(shadow, w.win, k);
     }
-    pages = leaf_end + branch_pages(leaves.size(), P);
+    const uint64_t pages = shadow.next_page + branch_pages(shadow.leaves, P), bytes = pages * P;
+    *len_out = (size_t)bytes;
+    if (stats) {
+      stats[0] = n;
+      stats[1] = shadow.leaves;
+      stats[2] = pages;
+    }
+    if (bytes > store_max_bytes())
+      return fail(DH_ENOMEM, "store image of %llu bytes exceeds DRANDHIP_STORE_MAX_BYTES (%zu)", (unsigned long long)bytes, store_max_bytes());
+    if (cap < bytes || !image_out) return fail(DH_EINVAL, "store image of %llu bytes, room for %zu", (unsigned long long)bytes, cap);
   }
-  const uint64_t bytes = pages * P;
-  *len_out = (size_t)bytes;
-  if (stats) {
-    stats[0] = n;
-    stats[1] = leaves.size();
-    stats[2] = pages;
+  for (size_t off = 0; off < n; off += W) {
+    prof_wall p(stage[3]);
+    const size_t k = std::min(W, n - off);
+    const bool final = off + k == n;
+    const uint64_t at = w.plan.next_page * P;  // the run's place in the image
+    size_t len = 0;
+    w.call_base = at;
+    int rc = bw_append(w, st, cut(off), k, final, image_out ? image_out + at : nullptr, cap > at ? cap - at : 0, &len, nullptr, image_out,
+                       final ? stats : nullptr, stage);
+    if (n <= W) {  // one window: sized here; the run starts at page 4
+      *len_out = len ? (size_t)at + len : 0;
+      if (rc == DH_EINVAL && len && (cap < at + len || !image_out))
+        return fail(DH_EINVAL, "store image of %llu bytes, room for %zu", (unsigned long long)(at + len), cap);
+    }
+    if (rc) return rc;
   }
-  if (bytes > store_max_bytes())
-    return fail(DH_ENOMEM, "store image of %llu bytes exceeds DRANDHIP_STORE_MAX_BYTES (%zu)", (unsigned long long)bytes, store_max_bytes());
-  if (cap < bytes || !image_out) return fail(DH_EINVAL, "store image of %llu bytes, room for %zu", (unsigned long long)bytes, cap);
-  const size_t nl = leaves.size();
-  const uint64_t leaf_bytes = (leaf_end - FIRST_LEAF_PAGE) * P;
-  std::vector<uint64_t> keys(nl), pgids(nl);
-  {
-    prof_wall p(stage[1]);
-    HIP_TRY(ws.leaves.ensure(nl * sizeof(leaf_desc)));
-    HIP_TRY(ws.image.ensure(leaf_bytes));
-    HIP_TRY(ws.keys.ensure(nl * 8));
-    HIP_TRY(hipMemcpyAsync(ws.leaves.p, leaves.data(), nl * sizeof(leaf_desc), hipMemcpyHostToDevice, st));
-    timed_launches tl(st);
-    HIP_TRY(tl.run("k_bolt_pack", [&] {
-      return dh::launch_bolt_pack(ws.leaves.p, nl, d_rounds, d_rows, stride, d_lens, P, ws.image.as<uint8_t>(), ws.keys.as<uint64_t>(), st);
-    }));
-    HIP_TRY(hipStreamSynchronize(st));
-  }
-  prof_wall p(stage[2]);
-  HIP_TRY(hipMemcpyAsync(image_out + FIRST_LEAF_PAGE * P, ws.image.p, leaf_bytes, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(keys.data(), ws.keys.p, nl * 8, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  for (size_t i = 0; i < nl; i++) pgids[i] = leaves[i].page;
-  finish_image(image_out, P, pages, leaf_end, keys.data(), pgids.data(), nl);
   return DH_OK;
 }
 
@@ -3644,143 +3851,430 @@ int dh_bolt_write_trimmed_device(const uint64_t* d_rounds, const uint8_t* d_rows
   if (hip_stream) HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));  // the columns may still be written there
   hipStream_t st = nullptr;
   HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  write_ws ws;
-  static const char* const stage[3] = {"bolt_write_plan", "bolt_write_pack", "bolt_write_download"};
-  rc = bolt_write_core(st, ws, d_rounds, d_rows, row_stride, d_lens, n, page_size, image_out, cap, len_out, stats_out, stage);
-  ws.release();
+  bw_state w;
+  static const char* const stage[4] = {"bolt_write_plan", "bolt_write_pack", "bolt_write_download", "bolt_write_window"};
+  rc = bolt_write_core(st, w, d_rounds, d_rows, row_stride, d_lens, n, page_size, image_out, cap, len_out, stats_out, stage);
+  w.release();
   (void)hipStreamDestroy(st);
   return rc;
+}
+
+// entered with w->mu held
+static int writer_enter(dh_bolt_writer* w) {
+  if (w->retire.exchange(false)) w->release();
+  if (w->dead) return fail(DH_EINVAL, "writer handle invalidated by dh_shutdown (dh_bolt_writer_close it and open again)");
+  HIP_TRY(hipSetDevice(g_ctx.device));
+  return DH_OK;
+}
+struct writer_guard {
+  dh_bolt_writer* w;
+  explicit writer_guard(dh_bolt_writer* x) : w(x) { w->mu.lock(); }
+  ~writer_guard() {
+    if (w->retire.exchange(false)) w->release();
+    w->mu.unlock();
+  }
+};
+static const char* const g_writer_stage[4] = {"bolt_write_plan", "bolt_write_pack", "bolt_write_download", "bolt_write_window"};
+
+int dh_bolt_writer_open(uint32_t page_size, dh_bolt_writer** out) {
+  if (!out) return fail(DH_EINVAL, "null argument");
+  *out = nullptr;
+  if (!dh::boltw::page_size_ok(page_size)) return fail(DH_EINVAL, "page size %u: a power of two from 256 to 65536", page_size);
+  int rc = ensure_device();
+  if (rc) return rc;
+  dh_bolt_writer* w = new dh_bolt_writer();
+  hipError_t e = hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking);
+  if (e != hipSuccess) {
+    delete w;
+    return fail(DH_EDEVICE, "hipStreamCreateWithFlags: %s", hipGetErrorString(e));
+  }
+  w->bw.reset(page_size);
+  std::lock_guard<std::mutex> lk(g_stores_mu);
+  g_writers.push_back(w);
+  *out = w;
+  return DH_OK;
+}
+
+int dh_bolt_writer_append_device(dh_bolt_writer* w, const uint64_t* d_rounds, const uint8_t* d_rows, size_t row_stride,
+                                 const uint32_t* d_lens, size_t n, uint8_t* out, size_t cap, size_t* len_out, uint64_t* file_off_out,
+                                 uint64_t stats_out[3], void* hip_stream) {
+  if (!w || !len_out) return fail(DH_EINVAL, "null argument");
+  *len_out = 0;
+  if ((n && (!d_rounds || !d_lens || (row_stride && !d_rows))) || (cap && !out)) return fail(DH_EINVAL, "null argument");
+  writer_guard g(w);
+  int rc = writer_enter(w);
+  if (rc) return rc;
+  if (n && hip_stream) HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));  // the columns may still be written there
+  prof_wall p(g_writer_stage[3]);
+  const dh::boltw::cols fresh{d_rounds, d_rows, (uint64_t)row_stride, d_lens};
+  return bw_append(w->bw, w->st, fresh, n, false, out, cap, len_out, file_off_out, nullptr, stats_out, g_writer_stage);
+}
+
+int dh_bolt_writer_finish(dh_bolt_writer* w, uint8_t* tail_out, size_t cap, size_t* len_out, uint64_t* file_off_out, uint8_t* head_out,
+                          uint64_t stats_out[3]) {
+  if (!w || !len_out) return fail(DH_EINVAL, "null argument");
+  *len_out = 0;
+  if (cap && !tail_out) return fail(DH_EINVAL, "null argument");
+  writer_guard g(w);
+  int rc = writer_enter(w);
+  if (rc) return rc;
+  const dh::boltw::cols none{nullptr, nullptr, 0, nullptr};
+  return bw_append(w->bw, w->st, none, 0, true, tail_out, cap, len_out, file_off_out, head_out, stats_out, g_writer_stage);
+}
+
+void dh_bolt_writer_close(dh_bolt_writer* w) {
+  if (!w) return;
+  {
+    std::lock_guard<std::mutex> lk(g_stores_mu);
+    g_writers.erase(std::remove(g_writers.begin(), g_writers.end(), w), g_writers.end());
+  }
+  {
+    std::lock_guard<std::mutex> lk(w->mu);
+    if (!w->dead && hipSetDevice(g_ctx.device) == hipSuccess) w->release();
+  }
+  delete w;
+}
+
+struct patch_list {
+  const uint64_t* rounds;
+  const uint8_t* sigs;
+  size_t stride;
+  const uint32_t* lens;
+  size_t n;
+  uint32_t longest;
+};
+
+// patches strictly ascending and inside [first, last]; sets p->longest
+static int patches_check(patch_list* p, uint64_t first, uint64_t last) {
+  if (p->n > ((size_t)1 << 20)) return fail(DH_EINVAL, "%zu patches: at most 2^20", p->n);
+  if (p->n && (!p->rounds || !p->lens)) return fail(DH_EINVAL, "null patch list");
+  if (p->stride > ((size_t)1 << 20)) return fail(DH_EINVAL, "patch stride %zu above 1 MiB", p->stride);
+  p->longest = 0;
+  for (size_t i = 0; i < p->n; i++) {
+    if (p->rounds[i] < first || p->rounds[i] > last || (i && p->rounds[i - 1] >= p->rounds[i]))
+      return fail(DH_EINVAL, "patch %zu (round %llu): patches are strictly ascending and inside [first, last]", i,
+                  (unsigned long long)p->rounds[i]);
+    if (p->lens[i] == DH_PATCH_DELETE) continue;
+    if (p->lens[i] > p->stride || (p->lens[i] && !p->sigs))
+      return fail(DH_EINVAL, "patch %zu: %u bytes, patch stride %zu", i, p->lens[i], p->stride);
+    p->longest = std::max(p->longest, p->lens[i]);
+  }
+  return DH_OK;
+}
+
+// the patches of [lo, hi] out of a checked list
+static patch_list patches_cut(const patch_list& p, uint64_t lo, uint64_t hi) {
+  const size_t a = std::lower_bound(p.rounds, p.rounds + p.n, lo) - p.rounds;
+  const size_t b = std::upper_bound(p.rounds, p.rounds + p.n, hi) - p.rounds;
+  patch_list q = p;
+  q.rounds = p.rounds + a;
+  q.lens = p.lens + a;
+  q.sigs = p.sigs ? p.sigs + a * p.stride : nullptr;
+  q.n = b - a;
+  return q;
+}
+
+struct merged {  // one round window merged with its patches: the columns are ws.o_*, the unlinked rounds ws.unl
+  size_t slots = 0, n_out = 0, n_unl = 0, n_hit = 0, n_ins = 0, o_stride = 4;
+};
+
+// The round records of first..last merged with the patches into s->wws.o_* (DESIGN.md §22). pred (device, nullable):
+// the row before the window, in the layout of carry_out.last, for the first merged row's unlinked test. A window
+// without a row is DH_OK with n_out = 0. Entered with the store held and the device set.
+static int store_merge_window(dh_store* s, uint64_t first, uint64_t last, const patch_list& pt, const uint64_t* pred, merged* out) {
+  write_ws& ws = s->wws;
+  const bool json = s->format == DH_STORE_UNTRIMMED;
+  const size_t n_patch = pt.n, patch_stride = pt.stride;
+  *out = merged();
+  prof_wall p("store_save_merge");
+  int rc;
+  size_t lo, nw, total;
+  uint32_t longest;
+  if ((rc = store_window(s, first, last, &lo, &nw, &total, &longest))) return rc;
+  if (total + n_patch + 3 > (size_t)4096 * 4096)
+    return fail(DH_EINVAL, "%zu rows and %zu patches: at most 16M per window", total, n_patch);
+  if (json) longest = window_longest_json(s, lo, nw);
+  const size_t stride = std::max<size_t>(4, ((size_t)longest + 3) & ~(size_t)3);
+  if (stride > ((size_t)1 << 20)) return fail(DH_EINVAL, "a %u-byte record in rounds %llu..%llu: keep the host reader", longest,
+                                              (unsigned long long)first, (unsigned long long)last);
+  HIP_TRY(s->rounds.ensure(total * 8 + 8));
+  HIP_TRY(s->rows.ensure(total * stride + 8));
+  HIP_TRY(s->lens.ensure(total * 4 + 4));
+  if (json) {
+    HIP_TRY(s->defer.ensure(total + 8));
+    HIP_TRY(s->prevs.ensure(total * stride + 8));
+    HIP_TRY(s->prev_lens.ensure(total * 4 + 4));
+    const dh::json_cols c{s->rounds.as<uint64_t>(), s->defer.as<uint8_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
+                          s->prevs.as<uint8_t>(), s->prev_lens.as<uint32_t>(), (uint32_t)stride, (uint32_t)stride, total};
+    if ((rc = store_gather_json(s, lo, nw, total, first, last, c, nullptr, 0))) return rc;
+  } else if ((rc = store_gather(s, lo, nw, total, first, last, stride, s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(),
+                                s->lens.as<uint32_t>(), total, nullptr, 0))) {
+    return rc;
+  }
+  // the patches, uploaded as given
+  const size_t slots = total + n_patch;
+  out->slots = slots;
+  if (!slots) return DH_OK;
+  HIP_TRY(ws.p_rounds.ensure(n_patch * 8 + 8));
+  HIP_TRY(ws.p_lens.ensure(n_patch * 4 + 4));
+  HIP_TRY(ws.p_rows.ensure(n_patch * patch_stride + 8));
+  HIP_TRY(ws.flag.ensure(slots * 4 + 4));
+  HIP_TRY(ws.lb.ensure(slots * 4 + 4));
+  HIP_TRY(ws.pos.ensure((slots + 1) * 4));
+  HIP_TRY(ws.scan_tmp.ensure((slots / 4096 + 2) * 4));
+  HIP_TRY(ws.hit.ensure(n_patch + 8));
+  HIP_TRY(ws.err.ensure(4));
+  if (n_patch) {
+    HIP_TRY(hipMemcpyAsync(ws.p_rounds.p, pt.rounds, n_patch * 8, hipMemcpyHostToDevice, s->st));
+    HIP_TRY(hipMemcpyAsync(ws.p_lens.p, pt.lens, n_patch * 4, hipMemcpyHostToDevice, s->st));
+    if (pt.sigs && patch_stride) HIP_TRY(hipMemcpyAsync(ws.p_rows.p, pt.sigs, n_patch * patch_stride, hipMemcpyHostToDevice, s->st));
+  }
+  HIP_TRY(hipMemsetAsync(ws.err.p, 0, 4, s->st));
+  const dh::merge_in m{s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
+                       json ? s->defer.as<uint8_t>() : nullptr, total, (uint32_t)stride, ws.p_rounds.as<uint64_t>(),
+                       ws.p_rows.as<uint8_t>(), ws.p_lens.as<uint32_t>(), n_patch, (uint32_t)patch_stride};
+  HIP_TRY(dh::launch_bolt_merge(m, ws.flag.as<uint32_t>(), ws.lb.as<uint32_t>(), ws.hit.as<uint8_t>(), ws.err.as<uint32_t>(), s->st));
+  HIP_TRY(dh::launch_scan(ws.flag.as<uint32_t>(), slots, ws.pos.as<uint32_t>(), ws.scan_tmp.as<uint32_t>(), s->st));
+  uint32_t err_word = 0, tot = 0;
+  std::vector<uint8_t> hit(n_patch);
+  HIP_TRY(hipMemcpyAsync(&err_word, ws.err.p, 4, hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipMemcpyAsync(&tot, ws.pos.as<uint32_t>() + slots, 4, hipMemcpyDeviceToHost, s->st));
+  if (n_patch) HIP_TRY(hipMemcpyAsync(hit.data(), ws.hit.p, n_patch, hipMemcpyDeviceToHost, s->st));
+  HIP_TRY(hipStreamSynchronize(s->st));
+  if (err_word) {
+    g_err = "a deferred record in the range is not covered by a patch (dh_store_deferred lists them)";
+    return DH_DEFERRED;
+  }
+  for (uint8_t h : hit) {
+    out->n_hit += h == 1;
+    out->n_ins += h == 2;
+  }
+  const size_t n_out = out->n_out = tot;
+  if (!n_out) return DH_OK;
+  const size_t o_stride = out->o_stride = std::max<size_t>(stride, ((size_t)pt.longest + 3) & ~(size_t)3);
+  HIP_TRY(ws.o_rounds.ensure(n_out * 8));
+  HIP_TRY(ws.o_rows.ensure(n_out * o_stride));
+  HIP_TRY(ws.o_lens.ensure(n_out * 4));
+  HIP_TRY(ws.o_src.ensure(n_out * 4));
+  const dh::merge_out o{ws.o_rounds.as<uint64_t>(), ws.o_rows.as<uint8_t>(), ws.o_lens.as<uint32_t>(), ws.o_src.as<uint32_t>(),
+                        (uint32_t)o_stride};
+  HIP_TRY(dh::launch_bolt_scatter(m, ws.flag.as<uint32_t>(), ws.lb.as<uint32_t>(), ws.pos.as<uint32_t>(), o, s->st));
+  if (json) {  // flag / pos are free again: the unlinked rows and their ranks
+    HIP_TRY(ws.flag.ensure(n_out * 4 + 4));
+    HIP_TRY(ws.pos.ensure((n_out + 1) * 4));
+    HIP_TRY(ws.unl.ensure(n_out * 8));
+    HIP_TRY(dh::launch_bolt_unlinked(o, n_out, s->prevs.as<uint8_t>(), (uint32_t)stride, s->prev_lens.as<uint32_t>(), pred,
+                                     ws.flag.as<uint32_t>(), s->st));
+    HIP_TRY(dh::launch_scan(ws.flag.as<uint32_t>(), n_out, ws.pos.as<uint32_t>(), ws.scan_tmp.as<uint32_t>(), s->st));
+    HIP_TRY(dh::launch_bolt_compact(ws.o_rounds.as<uint64_t>(), ws.pos.as<uint32_t>(), n_out, ws.unl.as<uint64_t>(), s->st));
+    HIP_TRY(hipMemcpyAsync(&tot, ws.pos.as<uint32_t>() + n_out, 4, hipMemcpyDeviceToHost, s->st));
+    HIP_TRY(hipStreamSynchronize(s->st));
+    out->n_unl = tot;
+  } else {
+    HIP_TRY(hipStreamSynchronize(s->st));
+  }
+  return DH_OK;
+}
+
+static dh::boltw::cols merged_cols(const write_ws& ws, const merged& m) {
+  return dh::boltw::cols{ws.o_rounds.as<uint64_t>(), ws.o_rows.as<uint8_t>(), (uint64_t)m.o_stride, ws.o_lens.as<uint32_t>()};
+}
+
+// [first, last] cut into round windows at leaf boundaries of the source, each of at most max(max_rows, rows of its
+// largest leaf) stored rows: window i = [b[2i], b[2i + 1]], the first from `first`, the last to `last`, no round between
+// two windows. From the leaf index and the scan's counts alone.
+static void store_split(const dh_store* s, uint64_t first, uint64_t last, size_t max_rows, std::vector<uint64_t>* b) {
+  b->clear();
+  if (first > last) return;
+  const auto& rl = s->rleaf;
+  const size_t lo = std::partition_point(rl.begin(), rl.end(), [&](uint32_t i) { return s->info[i].last < first; }) - rl.begin();
+  const size_t hi = std::partition_point(rl.begin(), rl.end(), [&](uint32_t i) { return s->info[i].first <= last; }) - rl.begin();
+  uint64_t start = first;
+  size_t rows = 0;
+  for (size_t k = lo; k < hi; k++) {
+    const auto& li = s->info[rl[k]];
+    if (rows && rows + li.n_round > max_rows) {  // cut behind the leaf before this one
+      const uint64_t end = s->info[rl[k - 1]].last;
+      b->push_back(start);
+      b->push_back(end);
+      start = end + 1;  // end < li.first <= last
+      rows = 0;
+    }
+    rows += li.n_round;
+  }
+  b->push_back(start);
+  b->push_back(last);
+}
+
+static const char* const g_save_stage[4] = {"store_save_plan", "store_save_pack", "store_save_download", "store_save_window"};
+
+int dh_store_split(dh_store* s, uint64_t first, uint64_t last, size_t max_rows, uint64_t* bounds_out, size_t cap, size_t* n_out) {
+  if (!s || !n_out || (cap && !bounds_out)) return fail(DH_EINVAL, "null argument");
+  *n_out = 0;
+  store_guard g(s);
+  int rc = store_enter(s);
+  if (rc) return rc;
+  std::vector<uint64_t> b;
+  store_split(s, first, last, std::max<size_t>(1, max_rows), &b);
+  *n_out = b.size() / 2;
+  if (*n_out > cap) return fail(DH_EINVAL, "%zu windows, room for %zu", *n_out, cap);
+  if (!b.empty()) memcpy(bounds_out, b.data(), b.size() * 8);
+  return DH_OK;
+}
+
+int dh_store_save_trimmed_append(dh_store* s, dh_bolt_writer* w, uint64_t first, uint64_t last, const uint64_t* patch_rounds,
+                                 const uint8_t* patch_sigs, size_t patch_stride, const uint32_t* patch_lens, size_t n_patch,
+                                 uint8_t* out, size_t cap, size_t* len_out, uint64_t* file_off_out, uint64_t* unlinked_out,
+                                 size_t unlinked_cap, size_t* n_unlinked_out, uint64_t stats_out[6]) {
+  if (!s || !w || !len_out || !n_unlinked_out || (cap && !out) || (unlinked_cap && !unlinked_out)) return fail(DH_EINVAL, "null argument");
+  *len_out = 0;
+  *n_unlinked_out = 0;
+  if (stats_out) memset(stats_out, 0, 6 * sizeof(uint64_t));
+  patch_list pt{patch_rounds, patch_sigs, patch_stride, patch_lens, n_patch, 0};
+  int rc = patches_check(&pt, first, last);
+  if (rc) return rc;
+  store_guard g(s);
+  if ((rc = store_enter(s))) return rc;
+  writer_guard gw(w);
+  if ((rc = writer_enter(w))) return rc;
+  bw_state& bw = w->bw;
+  if (file_off_out) *file_off_out = bw.plan.next_page * bw.P;
+  if (bw.finished) return fail(DH_EINVAL, "the writer is finished");
+  prof_wall p(g_save_stage[3]);
+  write_ws& ws = s->wws;
+  merged m;
+  const uint64_t* pred = bw.has_last ? bw.set[bw.cur].last.as<uint64_t>() : nullptr;
+  if ((rc = store_merge_window(s, first, last, pt, pred, &m))) return rc;
+  *n_unlinked_out = m.n_unl;
+  uint64_t st3[3] = {0, 0, 0};
+  if (m.n_out) {
+    const dh::boltw::cols fresh = merged_cols(ws, m);
+    if (m.n_unl > unlinked_cap) {  // sized without being taken
+      if ((rc = bw_plan_window(bw, s->st, bw.plan, fresh, m.n_out, pred, false, bw.win))) return rc;
+      *len_out = (size_t)((bw.win.next_page - bw.plan.next_page) * bw.P);
+      return fail(DH_EINVAL, "%zu unlinked rounds, room for %zu", m.n_unl, unlinked_cap);
+    }
+    if ((rc = bw_append(bw, s->st, fresh, m.n_out, false, out, cap, len_out, file_off_out, nullptr, st3, g_save_stage))) return rc;
+    if (m.n_unl) HIP_TRY(hipMemcpy(unlinked_out, ws.unl.p, m.n_unl * 8, hipMemcpyDeviceToHost));
+  }
+  if (stats_out) {
+    memcpy(stats_out, st3, sizeof st3);
+    stats_out[3] = m.n_unl;
+    stats_out[4] = m.n_hit;
+    stats_out[5] = m.n_ins;
+  }
+  return DH_OK;
 }
 
 int dh_store_save_trimmed(dh_store* s, uint64_t first, uint64_t last, const uint64_t* patch_rounds, const uint8_t* patch_sigs,
                           size_t patch_stride, const uint32_t* patch_lens, size_t n_patch, uint32_t page_size, uint8_t* image_out,
                           size_t cap, size_t* len_out, uint64_t* unlinked_out, size_t unlinked_cap, size_t* n_unlinked_out,
                           uint64_t stats_out[6]) {
+  using namespace dh::boltw;
   if (!s || !len_out || !n_unlinked_out || (cap && !image_out) || (unlinked_cap && !unlinked_out)) return fail(DH_EINVAL, "null argument");
   *len_out = 0;
   *n_unlinked_out = 0;
-  if (!dh::boltw::page_size_ok(page_size)) return fail(DH_EINVAL, "page size %u: a power of two from 256 to 65536", page_size);
-  if (n_patch > ((size_t)1 << 20)) return fail(DH_EINVAL, "%zu patches: at most 2^20", n_patch);
-  if (n_patch && (!patch_rounds || !patch_lens)) return fail(DH_EINVAL, "null patch list");
-  if (patch_stride > ((size_t)1 << 20)) return fail(DH_EINVAL, "patch stride %zu above 1 MiB", patch_stride);
-  uint32_t patch_longest = 0;
-  for (size_t i = 0; i < n_patch; i++) {
-    if (patch_rounds[i] < first || patch_rounds[i] > last || (i && patch_rounds[i - 1] >= patch_rounds[i]))
-      return fail(DH_EINVAL, "patch %zu (round %llu): patches are strictly ascending and inside [first, last]", i,
-                  (unsigned long long)patch_rounds[i]);
-    if (patch_lens[i] == DH_PATCH_DELETE) continue;
-    if (patch_lens[i] > patch_stride || (patch_lens[i] && !patch_sigs))
-      return fail(DH_EINVAL, "patch %zu: %u bytes, patch stride %zu", i, patch_lens[i], patch_stride);
-    patch_longest = std::max(patch_longest, patch_lens[i]);
-  }
+  if (!page_size_ok(page_size)) return fail(DH_EINVAL, "page size %u: a power of two from 256 to 65536", page_size);
+  patch_list pt{patch_rounds, patch_sigs, patch_stride, patch_lens, n_patch, 0};
+  int rc = patches_check(&pt, first, last);
+  if (rc) return rc;
   store_guard g(s);
-  int rc = store_enter(s);
-  if (rc) return rc;
+  if ((rc = store_enter(s))) return rc;
   write_ws& ws = s->wws;
-  const bool json = s->format == DH_STORE_UNTRIMMED;
-  size_t n_out = 0, n_unl = 0, n_hit = 0, n_ins = 0, o_stride = 4;
-  {
-    prof_wall p("store_save_merge");
-    size_t lo, nw, total;
-    uint32_t longest;
-    if ((rc = store_window(s, first, last, &lo, &nw, &total, &longest))) return rc;
-    if (total + n_patch + 3 > (size_t)4096 * 4096) return fail(DH_EINVAL, "%zu rows and %zu patches: at most 16M per call", total, n_patch);
-    if (json) longest = window_longest_json(s, lo, nw);
-    const size_t stride = std::max<size_t>(4, ((size_t)longest + 3) & ~(size_t)3);
-    if (stride > ((size_t)1 << 20)) return fail(DH_EINVAL, "a %u-byte record in rounds %llu..%llu: keep the host reader", longest,
-                                                (unsigned long long)first, (unsigned long long)last);
-    HIP_TRY(s->rounds.ensure(total * 8 + 8));
-    HIP_TRY(s->rows.ensure(total * stride + 8));
-    HIP_TRY(s->lens.ensure(total * 4 + 4));
-    if (json) {
-      HIP_TRY(s->defer.ensure(total + 8));
-      HIP_TRY(s->prevs.ensure(total * stride + 8));
-      HIP_TRY(s->prev_lens.ensure(total * 4 + 4));
-      const dh::json_cols c{s->rounds.as<uint64_t>(), s->defer.as<uint8_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
-                            s->prevs.as<uint8_t>(), s->prev_lens.as<uint32_t>(), (uint32_t)stride, (uint32_t)stride, total};
-      if ((rc = store_gather_json(s, lo, nw, total, first, last, c, nullptr, 0))) return rc;
-    } else if ((rc = store_gather(s, lo, nw, total, first, last, stride, s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(),
-                                  s->lens.as<uint32_t>(), total, nullptr, 0))) {
-      return rc;
-    }
-    // the patches, uploaded as given
-    const size_t slots = total + n_patch;
-    HIP_TRY(ws.p_rounds.ensure(n_patch * 8 + 8));
-    HIP_TRY(ws.p_lens.ensure(n_patch * 4 + 4));
-    HIP_TRY(ws.p_rows.ensure(n_patch * patch_stride + 8));
-    HIP_TRY(ws.flag.ensure(slots * 4 + 4));
-    HIP_TRY(ws.lb.ensure(slots * 4 + 4));
-    HIP_TRY(ws.pos.ensure((slots + 1) * 4));
-    HIP_TRY(ws.scan_tmp.ensure((slots / 4096 + 2) * 4));
-    HIP_TRY(ws.hit.ensure(n_patch + 8));
-    HIP_TRY(ws.err.ensure(4));
-    if (n_patch) {
-      HIP_TRY(hipMemcpyAsync(ws.p_rounds.p, patch_rounds, n_patch * 8, hipMemcpyHostToDevice, s->st));
-      HIP_TRY(hipMemcpyAsync(ws.p_lens.p, patch_lens, n_patch * 4, hipMemcpyHostToDevice, s->st));
-      if (patch_sigs && patch_stride)
-        HIP_TRY(hipMemcpyAsync(ws.p_rows.p, patch_sigs, n_patch * patch_stride, hipMemcpyHostToDevice, s->st));
-    }
-    HIP_TRY(hipMemsetAsync(ws.err.p, 0, 4, s->st));
-    const dh::merge_in m{s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
-                         json ? s->defer.as<uint8_t>() : nullptr, total, (uint32_t)stride, ws.p_rounds.as<uint64_t>(),
-                         ws.p_rows.as<uint8_t>(), ws.p_lens.as<uint32_t>(), n_patch, (uint32_t)patch_stride};
-    if (!slots) return fail(DH_ENOBEACON, "no beacon stored in rounds %llu..%llu", (unsigned long long)first, (unsigned long long)last);
-    HIP_TRY(dh::launch_bolt_merge(m, ws.flag.as<uint32_t>(), ws.lb.as<uint32_t>(), ws.hit.as<uint8_t>(), ws.err.as<uint32_t>(), s->st));
-    HIP_TRY(dh::launch_scan(ws.flag.as<uint32_t>(), slots, ws.pos.as<uint32_t>(), ws.scan_tmp.as<uint32_t>(), s->st));
-    uint32_t err_word = 0, tot = 0;
-    std::vector<uint8_t> hit(n_patch);
-    HIP_TRY(hipMemcpyAsync(&err_word, ws.err.p, 4, hipMemcpyDeviceToHost, s->st));
-    HIP_TRY(hipMemcpyAsync(&tot, ws.pos.as<uint32_t>() + slots, 4, hipMemcpyDeviceToHost, s->st));
-    if (n_patch) HIP_TRY(hipMemcpyAsync(hit.data(), ws.hit.p, n_patch, hipMemcpyDeviceToHost, s->st));
-    HIP_TRY(hipStreamSynchronize(s->st));
-    if (err_word) {
-      g_err = "a deferred record in the range is not covered by a patch (dh_store_deferred lists them)";
-      return DH_DEFERRED;
-    }
-    for (uint8_t h : hit) {
-      n_hit += h == 1;
-      n_ins += h == 2;
-    }
-    n_out = tot;
-    if (!n_out) return fail(DH_ENOBEACON, "no beacon left to write in rounds %llu..%llu", (unsigned long long)first, (unsigned long long)last);
-    o_stride = std::max<size_t>(stride, ((size_t)patch_longest + 3) & ~(size_t)3);
-    HIP_TRY(ws.o_rounds.ensure(n_out * 8));
-    HIP_TRY(ws.o_rows.ensure(n_out * o_stride));
-    HIP_TRY(ws.o_lens.ensure(n_out * 4));
-    HIP_TRY(ws.o_src.ensure(n_out * 4));
-    const dh::merge_out o{ws.o_rounds.as<uint64_t>(), ws.o_rows.as<uint8_t>(), ws.o_lens.as<uint32_t>(), ws.o_src.as<uint32_t>(),
-                          (uint32_t)o_stride};
-    HIP_TRY(dh::launch_bolt_scatter(m, ws.flag.as<uint32_t>(), ws.lb.as<uint32_t>(), ws.pos.as<uint32_t>(), o, s->st));
-    if (json) {  // flag / pos are free again: the unlinked rows and their ranks
-      HIP_TRY(ws.flag.ensure(n_out * 4 + 4));
-      HIP_TRY(ws.pos.ensure((n_out + 1) * 4));
-      HIP_TRY(ws.unl.ensure(n_out * 8));
-      HIP_TRY(dh::launch_bolt_unlinked(o, n_out, s->prevs.as<uint8_t>(), (uint32_t)stride, s->prev_lens.as<uint32_t>(),
-                                       ws.flag.as<uint32_t>(), s->st));
-      HIP_TRY(dh::launch_scan(ws.flag.as<uint32_t>(), n_out, ws.pos.as<uint32_t>(), ws.scan_tmp.as<uint32_t>(), s->st));
-      HIP_TRY(dh::launch_bolt_compact(ws.o_rounds.as<uint64_t>(), ws.pos.as<uint32_t>(), n_out, ws.unl.as<uint64_t>(), s->st));
-      HIP_TRY(hipMemcpyAsync(&tot, ws.pos.as<uint32_t>() + n_out, 4, hipMemcpyDeviceToHost, s->st));
+  bw_state& bw = ws.bw;
+  const uint32_t P = page_size;
+  // the windows: rows and patches of one window stay within the scan's reach
+  const size_t W = write_window_rows(), reach = (size_t)4096 * 4096 - 3 - n_patch;
+  std::vector<uint64_t> b;
+  store_split(s, first, last, std::max<size_t>(1, std::min(W, reach)), &b);
+  if (b.empty()) b = {first, last};  // first > last: the empty window, refused below
+  const size_t nwin = b.size() / 2;
+  bw.reset(P);
+  size_t slots = 0, rows = 0, n_unl = 0, n_hit = 0, n_ins = 0;
+  if (nwin > 1) {  // the whole image's size and the unlinked count, before a byte is written
+    bw_plan shadow;
+    HIP_TRY(ws.pred[0].ensure(16 + ((size_t)1 << 20)));
+    HIP_TRY(ws.pred[1].ensure(16 + ((size_t)1 << 20)));
+    int k = 0;
+    bool have = false;
+    for (size_t i = 0; i < nwin; i++) {
+      merged m;
+      const uint64_t* pred = have ? ws.pred[k].as<uint64_t>() : nullptr;
+      if ((rc = store_merge_window(s, b[2 * i], b[2 * i + 1], patches_cut(pt, b[2 * i], b[2 * i + 1]), pred, &m))) return rc;
+      slots += m.slots;
+      n_unl += m.n_unl;
+      n_hit += m.n_hit;
+      n_ins += m.n_ins;
+      if (!m.n_out) continue;
+      rows += m.n_out;
+      const cols fresh = merged_cols(ws, m);
+      prof_wall p(g_save_stage[0]);
+      if ((rc = bw_plan_window(bw, s->st, shadow, fresh, m.n_out, pred, false, bw.win))) return rc;
+      bw_advance(shadow, bw.win, m.n_out);
+      // the window's last row, for the next window's first
+      const cols2 c{fresh, fresh, 0};  // no carried rows: their segment gets readable addresses all the same
+      const dh::carry_out o{nullptr, nullptr, nullptr, 4, ws.pred[k ^ 1].as<uint64_t>(), (uint32_t)m.o_stride};
+      HIP_TRY(dh::launch_bolt_carry(c, 0, 0, m.n_out - 1, o, s->st));
       HIP_TRY(hipStreamSynchronize(s->st));
-      n_unl = tot;
-    } else {
-      HIP_TRY(hipStreamSynchronize(s->st));
+      k ^= 1;
+      have = true;
     }
+    if (rows) {
+      bw_window fin;  // the open leaf, closed
+      if ((rc = bw_plan_window(bw, s->st, shadow, cols{nullptr, nullptr, 0, nullptr}, 0, nullptr, true, fin))) return rc;
+      bw_advance(shadow, fin, 0);
+      const uint64_t pages = shadow.next_page + branch_pages(shadow.leaves, P), bytes = pages * P;
+      *len_out = (size_t)bytes;
+      *n_unlinked_out = n_unl;
+      if (stats_out) {
+        const uint64_t st6[6] = {rows, shadow.leaves, pages, n_unl, n_hit, n_ins};
+        memcpy(stats_out, st6, sizeof st6);
+      }
+      if (n_unl > unlinked_cap) return fail(DH_EINVAL, "%zu unlinked rounds, room for %zu", n_unl, unlinked_cap);
+      if (bytes > store_max_bytes())
+        return fail(DH_ENOMEM, "store image of %llu bytes exceeds DRANDHIP_STORE_MAX_BYTES (%zu)", (unsigned long long)bytes, store_max_bytes());
+      if (cap < bytes || !image_out) return fail(DH_EINVAL, "store image of %llu bytes, room for %zu", (unsigned long long)bytes, cap);
+    }
+    slots = rows = n_unl = n_hit = n_ins = 0;
   }
-  *n_unlinked_out = n_unl;
-  const bool room = n_unl <= unlinked_cap;
   uint64_t st3[3] = {0, 0, 0};
-  static const char* const stage[3] = {"store_save_plan", "store_save_pack", "store_save_download"};
-  rc = bolt_write_core(s->st, ws, ws.o_rounds.as<uint64_t>(), ws.o_rows.as<uint8_t>(), o_stride, ws.o_lens.as<uint32_t>(), n_out,
-                       page_size, room ? image_out : nullptr, room ? cap : 0, len_out, st3, stage);
-  if (stats_out) {
-    memcpy(stats_out, st3, sizeof st3);
-    stats_out[3] = n_unl;
-    stats_out[4] = n_hit;
-    stats_out[5] = n_ins;
+  for (size_t i = 0; i < nwin; i++) {
+    prof_wall p(g_save_stage[3]);
+    const bool final = i + 1 == nwin;
+    merged m;
+    const uint64_t* pred = bw.has_last ? bw.set[bw.cur].last.as<uint64_t>() : nullptr;
+    if ((rc = store_merge_window(s, b[2 * i], b[2 * i + 1], patches_cut(pt, b[2 * i], b[2 * i + 1]), pred, &m))) return rc;
+    slots += m.slots;
+    n_hit += m.n_hit;
+    n_ins += m.n_ins;
+    rows += m.n_out;
+    if (final && !rows) {
+      if (!slots) return fail(DH_ENOBEACON, "no beacon stored in rounds %llu..%llu", (unsigned long long)first, (unsigned long long)last);
+      return fail(DH_ENOBEACON, "no beacon left to write in rounds %llu..%llu", (unsigned long long)first, (unsigned long long)last);
+    }
+    if (!m.n_out && !final) continue;
+    const cols fresh = m.n_out ? merged_cols(ws, m) : cols{nullptr, nullptr, 0, nullptr};
+    const uint64_t at = bw.plan.next_page * P;  // the run's place in the image
+    const bool room = n_unl + m.n_unl <= unlinked_cap;  // more than one window: settled by the sizing pass
+    size_t len = 0;
+    bw.call_base = at;
+    rc = bw_append(bw, s->st, fresh, m.n_out, final, room && image_out ? image_out + at : nullptr, room && cap > at ? cap - at : 0, &len,
+                   nullptr, room ? image_out : nullptr, final ? st3 : nullptr, g_save_stage);
+    if (nwin == 1) {  // one window: sized here
+      *len_out = len ? (size_t)at + len : 0;
+      *n_unlinked_out = m.n_unl;
+      if (stats_out) {
+        const uint64_t st6[6] = {st3[0], st3[1], st3[2], m.n_unl, n_hit, n_ins};
+        memcpy(stats_out, st6, sizeof st6);
+      }
+      if (!room) return fail(DH_EINVAL, "%zu unlinked rounds, room for %zu", m.n_unl, unlinked_cap);
+      if (rc == DH_EINVAL && len && (cap < at + len || !image_out))
+        return fail(DH_EINVAL, "store image of %llu bytes, room for %zu", (unsigned long long)(at + len), cap);
+    }
+    if (rc) return rc;
+    if (m.n_unl) HIP_TRY(hipMemcpy(unlinked_out + n_unl, ws.unl.p, m.n_unl * 8, hipMemcpyDeviceToHost));
+    n_unl += m.n_unl;
   }
-  if (!room) return fail(DH_EINVAL, "%zu unlinked rounds, room for %zu", n_unl, unlinked_cap);
-  if (rc) return rc;
-  if (n_unl) HIP_TRY(hipMemcpy(unlinked_out, ws.unl.p, n_unl * 8, hipMemcpyDeviceToHost));
   return DH_OK;
 }
 

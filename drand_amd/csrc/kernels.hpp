@@ -319,7 +319,8 @@ hipError_t launch_bolt_fold_json(const uint32_t* sig_lens, const uint8_t* deferr
 // 0xFFFFFFFF = delete); flag / lb per slot (n + np words each), hit per patch, err_word set by a deferred row no patch
 // covers; then launch_scan over flag (pos, n + np + 1 words) and scatter into merge_out (stride a multiple of 4
 // holding every value; src = the stored row a merged row came from, 0xFFFFFFFF for a patch). unlinked: flag per
-// merged row (then launch_scan and compact: the flagged rounds, ascending).
+// merged row (then launch_scan and compact: the flagged rounds, ascending); pred (nullable) = the row before the first
+// merged row, in the layout of carry_out.last.
 struct merge_in {
   const uint64_t* rounds;
   const uint8_t* rows;
@@ -340,15 +341,32 @@ struct merge_out {
   uint32_t* src;
   uint32_t stride;
 };
-hipError_t launch_bolt_need(const uint64_t* rounds, const uint32_t* lens, size_t n, uint64_t stride, uint32_t* need, uint32_t* err_word,
-                            hipStream_t st);
-hipError_t launch_bolt_pack(const void* leaves, size_t n_leaves, const uint64_t* rounds, const uint8_t* rows, uint64_t stride,
-                            const uint32_t* lens, uint32_t page_size, uint8_t* image, uint64_t* first_key, hipStream_t st);
+// The windowed writer: need sizes and checks a window's n new rows (boltw::cols), the first of them
+// against last[0] (nullable here; the kernel always gets a readable address). pack and carry take the rows as
+// boltw::cols2 (bolt_write.hpp): the carried rows, then the caller's columns; n_carry = 0 is the one-shot call. pack: `image` starts at page page_base. carry: rows [first, first + count) into the
+// other carry set (stride a multiple of 4 holding their values) and row last_row into `last` = {round, length, then
+// the value from byte 16 at last_stride}; it reads nothing that it or the pack writes.
+namespace boltw {
+struct cols;
+struct cols2;
+}
+struct carry_out {
+  uint64_t* rounds;
+  uint32_t* lens;
+  uint8_t* rows;
+  uint32_t stride;
+  uint64_t* last;
+  uint32_t last_stride;
+};
+hipError_t launch_bolt_need(const boltw::cols& c, size_t n, const uint64_t* last, uint32_t* need, uint32_t* err_word, hipStream_t st);
+hipError_t launch_bolt_pack(const void* leaves, size_t n_leaves, const boltw::cols2& c, uint32_t page_size, uint64_t page_base,
+                            uint8_t* image, uint64_t* first_key, hipStream_t st);
+hipError_t launch_bolt_carry(const boltw::cols2& c, uint64_t first, uint64_t count, uint64_t last_row, const carry_out& o, hipStream_t st);
 hipError_t launch_bolt_merge(const merge_in& m, uint32_t* flag, uint32_t* lb, uint8_t* hit, uint32_t* err_word, hipStream_t st);
 hipError_t launch_bolt_scatter(const merge_in& m, const uint32_t* flag, const uint32_t* lb, const uint32_t* pos, const merge_out& o,
                                hipStream_t st);
 hipError_t launch_bolt_unlinked(const merge_out& o, size_t n_out, const uint8_t* prevs, uint32_t prev_stride, const uint32_t* prev_lens,
-                                uint32_t* flag, hipStream_t st);
+                                const uint64_t* pred, uint32_t* flag, hipStream_t st);
 hipError_t launch_bolt_compact(const uint64_t* rounds, const uint32_t* off, size_t n, uint64_t* out, hipStream_t st);
 
 #ifdef DH_COUNT_PRODUCTS

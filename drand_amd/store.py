@@ -502,7 +502,52 @@ class DeviceBoltStore:
         raw = self._raw(int(round_))
         return beacon_from_hexjson(raw).signature if self.untrimmed else raw
 
-    def save_trimmed(self, path, first=0, last=None, patches=None, page_size=4096):
+    def split(self, first=0, last=None, max_rows=1 << 20):
+        """dh_store_split: [(first, last)] round windows covering first..last, cut at leaf boundaries of the file, each
+        of at most max(max_rows, rows of its largest leaf) stored rows."""
+        lib = _lib.load()
+        first = int(first)
+        last = (1 << 64) - 1 if last is None else int(last)
+        n = ctypes.c_size_t(0)
+        rc = lib.dh_store_split(self._h, first, last, int(max_rows), None, 0, ctypes.byref(n))
+        if rc != _lib.DH_EINVAL or not n.value:
+            self._raise(rc)
+            return []
+        out = np.zeros(2 * n.value, np.uint64)
+        self._raise(lib.dh_store_split(self._h, first, last, int(max_rows), ctypes.c_void_p(out.ctypes.data), n.value, ctypes.byref(n)))
+        return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(n.value)]
+
+    def _resolve(self, first, last, patches, undecodable):
+        """After DH_DEFERRED: the deferred records of first..last that no patch covers, decoded by the host decoder into
+        `patches` (None and listed in `undecodable` when it rejects them)."""
+        todo = [k for k in self.deferred(first, last) if k not in patches]
+        if not todo:
+            raise RuntimeError("dh_store_save_trimmed keeps deferring records that are patched")
+        for k in todo:
+            try:
+                patches[k] = beacon_from_hexjson(self._raw(k)).signature
+            except DECODE_ERRORS:
+                patches[k] = None
+                undecodable.append(k)
+
+    def _save_trimmed_windows(self, path, first, last, patches, page_size, window):
+        stats = {"rows": 0, "leaves": 0, "pages": 0, "replaced_or_deleted": 0, "inserted": 0, "unlinked": [], "undecodable": []}
+        with BoltWriter(path, page_size) as w:
+            # a window's run: its records (16 B of element and 8 B of key each) plus the leaves' headers and padding,
+            # below a twelfth more for the page sizes and values of beacon stores; an outgrown buffer only costs a retry
+            longest = self._jstat[2] if self.untrimmed else self._stat[4]
+            longest = max([longest] + [len(v) for v in patches.values() if v is not None])
+            w.reserve((min(window, self._stat[1]) + len(patches) + 64) * (24 + longest) * 13 // 12 + 8 * page_size)
+            for lo, hi in self.split(first, last, window):
+                res = w.append_from(self, lo, hi, {r: v for r, v in patches.items() if lo <= r <= hi})
+                for k in ("replaced_or_deleted", "inserted"):
+                    stats[k] += res[k]
+                stats["unlinked"] += res["unlinked"]
+                stats["undecodable"] += res["undecodable"]
+            stats.update(w.finish())
+        return stats
+
+    def save_trimmed(self, path, first=0, last=None, patches=None, page_size=4096, window=None):
         """dh_store_save_trimmed: the round records of first..last as a trimmed store file at `path` (written to
         path + ".tmp", then os.replace). A trimmed store is copied value by value; an untrimmed one is converted: each
         record's decoded Signature under the record's key. patches: {round: bytes | None} replaces or inserts the
@@ -515,12 +560,22 @@ class DeviceBoltStore:
         Returns {"rows", "leaves", "pages", "replaced_or_deleted", "inserted", "unlinked", "undecodable"}. "unlinked":
         the rounds whose record stored a PreviousSig that the written file's record of round - 1 does not equal (or does
         not hold): a chained verifier reading the new file sees another previous signature for them than the old record
-        carried. Always empty for a trimmed source. `path` may not be the store's own file."""
+        carried. Always empty for a trimmed source. `path` may not be the store's own file.
+
+        window: stored rows per window of the streaming writer (BoltWriter over split()): the file is written to the
+        disk run by run with one window in host and device memory, and is the same file; the result is the same dict.
+        Without it the image is built in one call, unless the store holds more rows than one call takes."""
         lib = _lib.load()
         _refuse_same_file(path, self.path)
         first = int(first)
         last = (1 << 64) - 1 if last is None else int(last)
-        patches = dict(patches or {})
+        patches = {int(r): v for r, v in dict(patches or {}).items()}
+        if window is None and self._stat[1] + len(patches) > MAX_CALL_ROWS - 1:
+            window = STREAM_WINDOW
+        if window is not None:
+            if int(window) < 1:
+                raise ValueError("window: at least 1 row")
+            return self._save_trimmed_windows(path, first, last, patches, int(page_size), int(window))
         undecodable = []
         cap = int(os.path.getsize(self.path)) + 2 * sum(len(v) for v in patches.values() if v is not None) + 64 * int(page_size)
         ucap = 1024
@@ -535,15 +590,7 @@ class DeviceBoltStore:
                                            ctypes.c_void_p(image.ctypes.data), cap, ctypes.byref(n),
                                            ctypes.c_void_p(unl.ctypes.data), ucap, ctypes.byref(nu), stats)
             if rc == _lib.DH_DEFERRED:  # decided by the host decoder, once
-                todo = [k for k in self.deferred(first, last) if k not in patches]
-                if not todo:
-                    raise RuntimeError("dh_store_save_trimmed keeps deferring records that are patched")
-                for k in todo:
-                    try:
-                        patches[k] = beacon_from_hexjson(self._raw(k)).signature
-                    except DECODE_ERRORS:
-                        patches[k] = None
-                        undecodable.append(k)
+                self._resolve(first, last, patches, undecodable)
                 continue
             if rc == _lib.DH_EINVAL and (n.value > cap or nu.value > ucap):
                 cap, ucap = max(cap, n.value), max(ucap, nu.value)
@@ -587,14 +634,9 @@ def _patch_arrays(patches):
     return rounds, sigs, lens, stride
 
 
-def write_trimmed_bolt(path, rounds, sigs, lens=None, page_size=4096):
-    """dh_bolt_write_trimmed_device: a trimmed store file (chain/boltdb/trimmed.go:87-107 of the reference: bucket
-    "beacons", key = round, value = signature) from columns: rounds u64[n] strictly ascending, sigs u8[n, stride],
-    lens u32[n] (default: every value is the full row). numpy arrays are uploaded; torch tensors on the device (rounds
-    int64 carrying the u64 bit pattern, lens int32, as DeviceBoltStore.columns_device returns them) are used in place.
-    Written to path + ".tmp", then os.replace. Returns {"rows", "leaves", "pages"}."""
+def _device_columns(rounds, sigs, lens):
+    """(d_rounds int64[n], d_sigs uint8[n, stride], d_lens int32[n]) on the device; tensors are used in place."""
     import torch
-    lib = _lib.load()
     dev = torch.device("cuda")
 
     def tensor(x, np_dtype, view):
@@ -607,14 +649,174 @@ def write_trimmed_bolt(path, rounds, sigs, lens=None, page_size=4096):
     n = d_rounds.numel()
     if d_sigs.dim() != 2 or d_sigs.shape[0] != n or d_sigs.dtype != torch.uint8 or d_rounds.dtype != torch.int64:
         raise ValueError("rounds int64/uint64 [n] and sigs uint8 [n, stride]")
-    stride = int(d_sigs.shape[1])
     if lens is None:
-        d_lens = torch.full((n,), stride, dtype=torch.int32, device=dev)
+        d_lens = torch.full((n,), int(d_sigs.shape[1]), dtype=torch.int32, device=dev)
     else:
         d_lens = tensor(lens, np.uint32, np.int32).reshape(-1)
         if d_lens.numel() != n or d_lens.dtype != torch.int32:
             raise ValueError("lens int32/uint32 [n]")
     torch.cuda.synchronize()
+    return d_rounds, d_sigs, d_lens
+
+
+# Rows per window of the streaming paths (write_trimmed_bolt / save_trimmed / correct_store_file with window=None and a
+# source above one call's rows): the fastest window of the sweep of bench/store_stream.py (1M, 4M and 8M rows) in its
+# 8M-row rewrite, the one case in which the windows differ; no larger one lies inside its spread (DESIGN.md §23,
+# profiles/r18/store_stream.json).
+STREAM_WINDOW = 1 << 20
+MAX_CALL_ROWS = 4096 * 4096 - 2  # what one library call takes: the device scan's limit
+
+
+class BoltWriter:
+    """The windowed writer (dh_bolt_writer_*): a trimmed store file written from rows that arrive in
+    windows. Each run of pages is written to path + ".tmp" at its offset as it arrives; finish() writes the tail, then
+    the head, and os.replace()s. The file is byte for byte what write_trimmed_bolt gives for the concatenated rows.
+    Host memory is one window's run, not the file. A context manager: on an exception, or on leaving the block without
+    finish(), the .tmp file is removed and `path` is untouched."""
+
+    def __init__(self, path, page_size=4096):
+        lib = _lib.load()
+        self.path, self.page_size = str(path), int(page_size)
+        self._tmp = self.path + ".tmp"
+        self._h = ctypes.c_void_p()
+        self._f = None
+        self._buf = np.empty(0, np.uint8)
+        DeviceBoltStore._raise(lib.dh_bolt_writer_open(self.page_size, ctypes.byref(self._h)))
+        try:
+            self._f = open(self._tmp, "wb")
+        except BaseException:
+            self.close()
+            raise
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        """Frees the handle; an unfinished file is removed."""
+        if self._h:
+            _lib.load().dh_bolt_writer_close(self._h)
+            self._h = ctypes.c_void_p()
+        if self._f is not None:
+            self._f.close()
+            self._f = None
+            if os.path.exists(self._tmp):
+                os.remove(self._tmp)
+
+    def _room(self, size):
+        if self._buf.size < size:
+            self._buf = np.empty(size, np.uint8)
+        return self._buf
+
+    def reserve(self, nbytes):
+        """Room for runs of up to nbytes in the one host buffer the appends share. An append whose run outgrows the
+        buffer is refused by the library, which consumes nothing, and is made again with the size it reported; for a
+        window of a store that repeats the window's gather and merge, so a caller that knows its windows reserves."""
+        self._room(int(nbytes))
+
+    def _emit(self, call):
+        """call(out, cap, len_ref, off_ref) -> rc, sized by a first refusal; the run is written at its offset."""
+        size, off = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        buf = self._buf
+        rc = call(ctypes.c_void_p(buf.ctypes.data) if buf.size else None, buf.size, ctypes.byref(size), ctypes.byref(off))
+        if rc == _lib.DH_EINVAL and size.value > buf.size:  # nothing was consumed
+            buf = self._room(size.value)
+            rc = call(ctypes.c_void_p(buf.ctypes.data), buf.size, ctypes.byref(size), ctypes.byref(off))
+        if rc in (_lib.DH_OK,) and size.value:
+            self._f.seek(off.value)
+            buf[:size.value].tofile(self._f)
+        return rc
+
+    def append(self, rounds, sigs, lens=None):
+        """Rows as write_trimmed_bolt takes them, above every round appended so far. Returns {"rows", "leaves",
+        "pages"}: the rows taken, the leaves this append closed and the pages it wrote."""
+        lib = _lib.load()
+        if self._f is None:
+            raise ValueError("the writer is closed")
+        d_rounds, d_sigs, d_lens = _device_columns(rounds, sigs, lens)
+        stats = (ctypes.c_uint64 * 3)()
+        args = (d_rounds.data_ptr() or None, d_sigs.data_ptr() or None, int(d_sigs.shape[1]), d_lens.data_ptr() or None, d_rounds.numel())
+        DeviceBoltStore._raise(self._emit(lambda out, cap, n, off: lib.dh_bolt_writer_append_device(self._h, *args, out, cap, n, off,
+                                                                                                  stats, None)))
+        return {"rows": int(stats[0]), "leaves": int(stats[1]), "pages": int(stats[2])}
+
+    def append_from(self, store, first, last, patches=None):
+        """dh_store_save_trimmed_append: the round records of first..last of an open DeviceBoltStore, merged with
+        patches {round: bytes | None} as save_trimmed takes them, deferred records resolved the same way. Windows come
+        in ascending round order. Returns {"rows", "leaves", "pages", "replaced_or_deleted", "inserted", "unlinked",
+        "undecodable"} of this window."""
+        lib = _lib.load()
+        if self._f is None:
+            raise ValueError("the writer is closed")
+        first, last = int(first), int(last)
+        patches = {int(r): v for r, v in dict(patches or {}).items()}
+        undecodable = []
+        ucap = 1024
+        while True:
+            pr, ps, pl, stride = _patch_arrays(patches)
+            unl = np.zeros(ucap, np.uint64)
+            nu = ctypes.c_size_t(0)
+            stats = (ctypes.c_uint64 * 6)()
+            rc = self._emit(lambda out, cap, n, off: lib.dh_store_save_trimmed_append(
+                store._h, self._h, first, last, ctypes.c_void_p(pr.ctypes.data), ctypes.c_void_p(ps.ctypes.data), stride,
+                ctypes.c_void_p(pl.ctypes.data), len(patches), out, cap, n, off, ctypes.c_void_p(unl.ctypes.data), ucap,
+                ctypes.byref(nu), stats))
+            if rc == _lib.DH_DEFERRED:  # decided by the host decoder, once
+                store._resolve(first, last, patches, undecodable)
+                continue
+            if rc == _lib.DH_EINVAL and nu.value > ucap:
+                ucap = nu.value
+                continue
+            DeviceBoltStore._raise(rc)
+            break
+        return {"rows": int(stats[0]), "leaves": int(stats[1]), "pages": int(stats[2]), "replaced_or_deleted": int(stats[4]),
+                "inserted": int(stats[5]), "unlinked": [int(x) for x in unl[:nu.value]], "undecodable": undecodable}
+
+    def finish(self):
+        """Writes the tail and the head, renames the file into place. Returns {"rows", "leaves", "pages"} of the file."""
+        lib = _lib.load()
+        if self._f is None:
+            raise ValueError("the writer is closed")
+        stats = (ctypes.c_uint64 * 3)()
+        head = np.empty(4 * self.page_size, np.uint8)
+        DeviceBoltStore._raise(self._emit(lambda out, cap, n, off: lib.dh_bolt_writer_finish(
+            self._h, out, cap, n, off, ctypes.c_void_p(head.ctypes.data), stats)))
+        self._f.seek(0)
+        head.tofile(self._f)
+        self._f.flush()
+        os.replace(self._tmp, self.path)  # if this raises, close() (the context manager's exit) removes the .tmp
+        self._f.close()
+        self._f = None
+        self.close()
+        return {"rows": int(stats[0]), "leaves": int(stats[1]), "pages": int(stats[2])}
+
+
+def write_trimmed_bolt(path, rounds, sigs, lens=None, page_size=4096, window=None):
+    """dh_bolt_write_trimmed_device: a trimmed store file (chain/boltdb/trimmed.go:87-107 of the reference: bucket
+    "beacons", key = round, value = signature) from columns: rounds u64[n] strictly ascending, sigs u8[n, stride],
+    lens u32[n] (default: every value is the full row). numpy arrays are uploaded; torch tensors on the device (rounds
+    int64 carrying the u64 bit pattern, lens int32, as DeviceBoltStore.columns_device returns them) are used in place.
+    Written to path + ".tmp", then os.replace. Returns {"rows", "leaves", "pages"}.
+
+    window: rows per append of a BoltWriter, which streams the file to the disk with one window's run in host memory;
+    the file is the same. Without it the image is built in one call, unless there are more rows than one call takes."""
+    lib = _lib.load()
+    d_rounds, d_sigs, d_lens = _device_columns(rounds, sigs, lens)
+    n = d_rounds.numel()
+    if window is None and n > MAX_CALL_ROWS:
+        window = STREAM_WINDOW
+    if window is not None:
+        window = int(window)
+        if window < 1 or window > MAX_CALL_ROWS:
+            raise ValueError("window: 1..%d rows" % MAX_CALL_ROWS)
+        with BoltWriter(path, page_size) as w:
+            for at in range(0, n, window):
+                w.append(d_rounds[at:at + window], d_sigs[at:at + window], d_lens[at:at + window])
+            return w.finish()
+    stride = int(d_sigs.shape[1])
     size = ctypes.c_size_t(0)
     stats = (ctypes.c_uint64 * 3)()
     args = (d_rounds.data_ptr() or None, d_sigs.data_ptr() or None, stride, d_lens.data_ptr() or None, n, int(page_size))

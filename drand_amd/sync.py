@@ -121,7 +121,7 @@ def check_past_beacons(store, scheme, pubkey, up_to, cb=None, window=1 << 20, se
     return faulty
 
 
-def correct_store_file(src, dst, scheme, pubkey, fetch, up_to=None, fmt="auto"):
+def correct_store_file(src, dst, scheme, pubkey, fetch, up_to=None, fmt="auto", window=None):
     """CheckPastBeacons followed by CorrectPastBeacons (chain/beacon/sync_manager.go:170-268 of the reference), offline,
     from the store file `src` to a new trimmed store file `dst` (the daemon is stopped, `dst` is renamed
     over `src` by the caller when it is satisfied):
@@ -132,6 +132,7 @@ def correct_store_file(src, dst, scheme, pubkey, fetch, up_to=None, fmt="auto"):
       4. only the records that verify become patches of DeviceBoltStore.save_trimmed(dst);
       5. `dst` is reopened and checked again.
     Returns (faulty_before, faulty_after, unlinked): the two checks' lists and save_trimmed's unlinked rounds.
+    window: save_trimmed's (stored rows per window of the streaming writer); the file is the same.
 
     Deviation from the reference: CorrectPastBeacons re-syncs the faulty rounds through the sync manager, where every
     streamed packet carries its own PreviousSig and is verified against it, and later packets can build on earlier
@@ -169,7 +170,7 @@ def correct_store_file(src, dst, scheme, pubkey, fetch, up_to=None, fmt="auto"):
             sigs = np.frombuffer(b"".join(fetched[r] for r in cand), np.uint8).reshape(len(cand), scheme.sig_len).copy()
             ok, _ = scheme.verify_beacons(pubkey, rounds, sigs, prevs, want_randomness=False)
             patches = {r: fetched[r] for r, v in zip(cand, ok) if v}
-        res = st.save_trimmed(dst, patches=patches)
+        res = st.save_trimmed(dst, patches=patches, window=window)
     with _store.DeviceBoltStore(dst, scheme.chained, fmt="trimmed") as out:
         faulty_after = out.check_past(scheme, pubkey, up_to)
     return faulty_before, faulty_after, res["unlinked"]

@@ -405,9 +405,12 @@ int dh_store_deferred(dh_store* store, uint64_t first, uint64_t last, uint64_t* 
  * d_rows + i*row_stride, d_lens[i] <= row_stride; a violation is DH_EINVAL, found on the device before anything is
  * written). page_size: a power of two from 256 to 65536, else DH_EINVAL. image_out: HOST memory of `cap` bytes;
  * *len_out = the size of the image, a multiple of page_size; cap too small: DH_EINVAL with *len_out set and nothing
- * written. n = 0: DH_ENOBEACON (no empty store is written). n above 16M rows: DH_EINVAL. An image above
- * DRANDHIP_STORE_MAX_BYTES or a failed allocation: DH_ENOMEM. stats_out (nullable) = {rows, leaves, pages}. Work queued
- * on hip_stream is waited for first; the call returns when the image is complete.
+ * written. n = 0: DH_ENOBEACON (no empty store is written). An image above DRANDHIP_STORE_MAX_BYTES or a failed
+ * allocation: DH_ENOMEM. stats_out (nullable) = {rows, leaves, pages}. Work queued on hip_stream is waited for first; the
+ * call returns when the image is complete. The call runs as a loop over the windowed writer below, in windows of
+ * DRANDHIP_STORE_WRITE_WINDOW rows (read at every call; default and upper bound: the device scan's limit of 16M rows;
+ * values below 1 are ignored), so n has no limit of its own; the image does not depend on the window. dh_profile stages:
+ * bolt_write_plan, bolt_write_pack, bolt_write_download, and bolt_write_window once per window.
  */
 #define DH_PATCH_DELETE 0xFFFFFFFFu
 int dh_bolt_write_trimmed_device(const uint64_t* d_rounds, const uint8_t* d_rows, size_t row_stride, const uint32_t* d_lens,
@@ -429,14 +432,87 @@ int dh_bolt_write_trimmed_device(const uint64_t* d_rounds, const uint8_t* d_rows
  * exactly the rounds for which the written file hands a chained verifier another previous signature than the record
  * stored. unlinked_out: those rounds, ascending; more than unlinked_cap: DH_EINVAL with *n_unlinked_out = the number
  * and *len_out = the image size, nothing written. Always empty for a trimmed handle.
- * image_out / cap / len_out / page_size and the limits as above (rows + patches below 16M). stats_out (nullable) =
- * {rows written, leaves, pages, unlinked, patches that replaced or deleted a record, patches that inserted one}.
- * dh_profile stages: store_save_merge, store_save_plan, store_save_pack, store_save_download.
+ * image_out / cap / len_out / page_size as above. stats_out (nullable) = {rows written, leaves, pages, unlinked, patches
+ * that replaced or deleted a record, patches that inserted one}. The call runs as a loop over the windowed writer
+ * below: the range is cut at leaf boundaries of the source (dh_store_split) into windows of at most
+ * DRANDHIP_STORE_WRITE_WINDOW stored rows (default: what keeps rows + patches of a window within the scan's 16M), so
+ * the range has no row limit of its own; more than one window costs a sizing pass over the range first. The image, the
+ * unlinked list and the stats do not depend on the window.
+ * dh_profile stages: store_save_merge, store_save_plan, store_save_pack, store_save_download, and store_save_window
+ * once per window.
  */
 int dh_store_save_trimmed(dh_store* store, uint64_t first, uint64_t last, const uint64_t* patch_rounds, const uint8_t* patch_sigs,
                           size_t patch_stride, const uint32_t* patch_lens, size_t n_patch, uint32_t page_size,
                           uint8_t* image_out, size_t cap, size_t* len_out, uint64_t* unlinked_out, size_t unlinked_cap,
                           size_t* n_unlinked_out, uint64_t stats_out[6]);
+
+/*
+ * The windowed writer: the same file, written from rows that arrive in windows, with bounded
+ * device memory and no row limit on the file (row counts and page ids are 64-bit; the host keeps 16 bytes per leaf).
+ * Every leaf is emitted as soon as it is closed, i.e. once a following record is known not to fit; the rows of the open
+ * leaf (at most page_size - 24 bytes of records) are carried in the writer to the next window; the branch levels and
+ * pages 0-3 are written by dh_bolt_writer_finish.
+ * THE FILE INVARIANT: out[0, *len_out) of every append belongs at file offset *file_off_out; the runs of successive
+ * appends are contiguous and start at 4 * page_size; the tail of dh_bolt_writer_finish follows the last run; head_out
+ * belongs at offset 0; and head || runs || tail is byte for byte the image dh_bolt_write_trimmed_device gives for the
+ * concatenated rows, for every split into appends, whatever their strides.
+ *
+ * dh_bolt_writer_open: page_size as above. dh_bolt_writer_close frees the handle (NULL is ignored). A handle is used by
+ * one call at a time; two handles run concurrently. dh_shutdown releases a handle's device memory: every later call on
+ * it fails with DH_EINVAL, and dh_bolt_writer_close still frees it.
+ *
+ * dh_bolt_writer_append_device: n rows in the layout of dh_bolt_write_trimmed_device, at most 16M a call, their rounds
+ * above every round appended before. out: HOST memory of `cap` bytes for the pages of the leaves this append closes;
+ * *len_out = their size (0 when it closes none); stats_out (nullable) = {rows taken, leaves closed, pages emitted}.
+ * n = 0 is DH_OK with *len_out = 0. DH_OK means the rows were taken. NOTHING IS CONSUMED ON FAILURE: with cap too small
+ * (cap 0 sizes) DH_EINVAL with *len_out = the size needed; rounds not strictly ascending, inside the append or against
+ * the last round appended, or a length above row_stride: DH_EINVAL; a run above DRANDHIP_STORE_MAX_BYTES (which bounds
+ * what one call emits, not the file) DH_ENOMEM; in each case the writer is exactly as before the call and a later
+ * correct call continues the same file. Work queued on hip_stream is waited for first; the columns are free again when
+ * the call returns.
+ *
+ * dh_bolt_writer_finish: closes the open leaf. tail_out: HOST memory of `cap` bytes for its pages and the branch pages,
+ * which belong at *file_off_out; head_out: 4 * page_size bytes of HOST memory for pages 0-3. cap too small (cap 0
+ * sizes) or head_out NULL: DH_EINVAL with *len_out = the size needed, nothing consumed. A writer that never received a
+ * row: DH_ENOBEACON. stats_out (nullable) = {rows, leaves, pages} of the file, as the one-shot call reports them. After
+ * DH_OK the writer takes no further call but dh_bolt_writer_close.
+ * dh_profile stages: bolt_write_plan, bolt_write_pack, bolt_write_download per append, bolt_write_window once per append.
+ */
+typedef struct dh_bolt_writer dh_bolt_writer;
+int dh_bolt_writer_open(uint32_t page_size, dh_bolt_writer** out);
+int dh_bolt_writer_append_device(dh_bolt_writer* w, const uint64_t* d_rounds, const uint8_t* d_rows, size_t row_stride,
+                                 const uint32_t* d_lens, size_t n, uint8_t* out, size_t cap, size_t* len_out,
+                                 uint64_t* file_off_out, uint64_t stats_out[3], void* hip_stream);
+int dh_bolt_writer_finish(dh_bolt_writer* w, uint8_t* tail_out, size_t cap, size_t* len_out, uint64_t* file_off_out,
+                          uint8_t* head_out, uint64_t stats_out[3]);
+void dh_bolt_writer_close(dh_bolt_writer* w);
+/*
+ * dh_store_save_trimmed_append: one round window first..last of an open store, merged with its patches exactly as
+ * dh_store_save_trimmed takes them, appended to a writer: a windowed convert or repair. Windows are passed in ascending
+ * round order (a window's first written round must pass the writer's last, else DH_EINVAL); one file may take windows
+ * of several stores and rows of dh_bolt_writer_append_device. out / cap / len_out / file_off_out as
+ * dh_bolt_writer_append_device. The first written row of a window is tested for UNLINKED against the last row the
+ * writer received: linked when that row is round - 1 and holds the stored PreviousSig, whichever window or patch it came
+ * from. unlinked_out: this window's unlinked rounds, ascending (so the lists of successive windows concatenate
+ * ascending). A window that produces no row (an empty range, or everything deleted) is DH_OK with *len_out = 0.
+ * Nothing is consumed on failure: DH_DEFERRED, a cap too small (DH_EINVAL, *len_out = the size needed), more than
+ * unlinked_cap unlinked rounds (DH_EINVAL, *n_unlinked_out = the number, *len_out = the size needed) and every other
+ * refusal leave the writer as before the call. A window holds at most 16M rows and 2^20 patches. stats_out (nullable) =
+ * {rows taken, leaves closed, pages emitted, unlinked, patches that replaced or deleted a record, patches that inserted}.
+ * The store handle and the writer are both held for the call.
+ *
+ * dh_store_split: [first, last] cut into n windows at leaf boundaries of the source file, ascending: window i is
+ * bounds_out[2i] .. bounds_out[2i + 1] inclusive, the first starts at `first`, the last ends at `last`, and window i + 1
+ * starts one above the end of window i, so every round (and every patch) of the range lies in exactly one window. Each
+ * window holds at most max(max_rows, rows of its largest leaf) stored rows. cap counts windows; too little room:
+ * DH_EINVAL with *n_out = the number needed. first > last: no window. From the open handle's leaf index and counts
+ * alone: no device work.
+ */
+int dh_store_save_trimmed_append(dh_store* store, dh_bolt_writer* w, uint64_t first, uint64_t last, const uint64_t* patch_rounds,
+                                 const uint8_t* patch_sigs, size_t patch_stride, const uint32_t* patch_lens, size_t n_patch,
+                                 uint8_t* out, size_t cap, size_t* len_out, uint64_t* file_off_out, uint64_t* unlinked_out,
+                                 size_t unlinked_cap, size_t* n_unlinked_out, uint64_t stats_out[6]);
+int dh_store_split(dh_store* store, uint64_t first, uint64_t last, size_t max_rows, uint64_t* bounds_out, size_t cap, size_t* n_out);
 
 /*
  * Synthetic-chain utilities (test fixtures and benchmark inputs; not part of the verification path):
