@@ -74,7 +74,9 @@ def main():
                          "k_sub_batch_level0<fp2>), which r09 had not carried into this file. r15: a large local G1 batch "
                          "runs its decode and its hash as one launch reported under k_prep_msg<fp> (DESIGN 20: the hash "
                          "point's inversion rides the decode's square-root chain), so k_prep_sig<fp> is 0 and "
-                         "k_prep_msg<fp> is the sum, counted against 463 + 1074 = 1537 for the two kernels before")
+                         "k_prep_msg<fp> is the sum, counted against 463 + 1074 = 1537 for the two kernels before. r19: "
+                         "level 0 of such a batch runs its MSM on one 63-bit half of each round's coefficient (DESIGN 24): "
+                         "msm_level0 is counted on 4 entries per point and set and 8 window rows, against 203.1 on 8 and 16")
     wm.pop("_doc_k_lagrange", None)
     with open(wm_path, "w") as f:
         json.dump(wm, f, indent=2)

@@ -782,7 +782,9 @@ static const std::vector<size_t>& fixed_ladder() {
 // group failed, 5 per group). The next size minimises the expected cost of the rest of the descent.
 static double msm_cost_ms(double m, size_t g) {
   const dh::msm_geom gg = geom_for(g, 2);
-  return 9.0 + 1.8e-6 * m * (double)(gg.nwin * gg.halves) / 2.0;  // fitted on 127-bit entries (8 per round at c = 16)
+  // fitted on 127-bit entries (8 per round at c = 16). Only the levels below level 0 are priced here, and they keep
+  // both scalar halves (the one-half level 0 of DESIGN §24 is never a candidate), so the entry count stays nwin x halves
+  return 9.0 + 1.8e-6 * m * (double)(gg.nwin * gg.halves) / 2.0;
 }
 static double check_cost_ms(double groups) { return 12.0 + 0.0025 * groups; }
 static double leaf_cost_ms(double m) { return 12.0 + 0.005 * m; }
@@ -936,6 +938,24 @@ static bool g1_iso_late_on() {
   return v;
 }
 
+// Level 0 of such a batch keys the a-half of each round's scalar alone: r_i = a_i, 63 bits, half the
+// sorted-list entries and window rows and no phi of a row sum. A level-0 accept is then wrong with probability at most
+// 2^-62 (the batched subgroup test's 2^-63 and the check's 2^-63); a batch that level 0 does not end is re-checked by
+// the fallback and the bisection on r_i = a_i + mu b_i, as before. DRANDHIP_G1_RLC_HALF=0 keeps both halves at level 0.
+static bool g1_rlc_half_on() {
+  static const bool v = [] {
+    const char* e = getenv("DRANDHIP_G1_RLC_HALF");
+    return !(e && e[0] == '0');
+  }();
+  return v;
+}
+// the shape of the calling thread's last level-0 MSM (dh_msm_level0_shape_debug)
+struct level0_shape {
+  uint64_t rows = 0, entries = 0;
+  int half_a = 0, half_b = 0;
+};
+static thread_local level0_shape g_level0;
+
 // MSM workspace of one bisection level (m entries in ngroups groups of geometry g, Jacobian width jw words); sub: also
 // the batched subgroup test's scratch (ws.sub)
 static int msm_workspace(worker* w, const dh::msm_geom& g, size_t m, size_t ngroups, size_t jw, dh::msm_ws& ws,
@@ -1005,6 +1025,7 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
   const int parts = g2 && !sub_batch ? 4 : 2;
   const bool g1_ride = !g2 && sub_batch && g1_ride_on();
   const bool iso_late = g1_ride && g1_iso_late_on();  // level 0 on split rows, the hash set on E1'
+  const bool rlc_half = iso_late && g1_rlc_half_on();  // and on the scalars' a-halves alone
   // sorted-list entries keep a sign bit and address parts * n points (the endomorphism images follow the n points)
   if (n >= ((size_t)1 << 31) / parts) return fail(DH_EINVAL, "batch too large");
   dh::msm_geom g0{};
@@ -1037,6 +1058,7 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
       g0 = geom_for(n, parts);
       g0.half_stride = (uint32_t)n;
       g0.split = iso_late ? 1 : 0;
+      g0.half0 = rlc_half ? 1 : 0;
       rc = msm_workspace(w, g0, n, 1, wsw, ws0, sub_batch, g2);
       if (rc) return rc;
       HIP_TRY(dh::launch_msm_sort(g0, w->entries.as<uint32_t>(), nullptr, nullptr, n, 1, w->scal.as<uint4>(), ws0, ts));
@@ -1130,6 +1152,7 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
     dh::msm_geom g = geom_for(gsize, parts);
     g.half_stride = (uint32_t)n;
     g.split = level == 0 && iso_late ? 1 : 0;
+    g.half0 = level == 0 && rlc_half ? 1 : 0;
     const size_t ngroups = (m + gsize - 1) / gsize;
     fit_segments(g, ngroups, 2);
     const bool pre = level == 0 && presorted;
@@ -1139,6 +1162,10 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
     } else {
       const int rc = msm_workspace(w, g, m, ngroups, wsw, ws, level == 0 && sub_batch, g2);
       if (rc) return rc;
+    }
+    if (level == 0 && mode == VM_FULL) {
+      const dh::msm_geom& gl = pre ? g0 : g;
+      g_level0 = level0_shape{dh::msm_rows(gl), dh::msm_entries(gl, m), 1, dh::msm_keyed(gl) > 1 ? 1 : 0};
     }
     if (!(level == 0 && mode >= VM_FINISH)) {  // a resumed batch has its level-0 sums from dh_batch_begin
       // every level skips the rounds whose status is not DEC_OK (their scalars are nonzero after a presort)
@@ -2885,6 +2912,15 @@ int dh_g1_round_prep_late_debug(const uint8_t* us, const uint8_t* sigs, size_t n
   HIP_TRY(hipMemcpyAsync(sig_out, out, n * 96, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(hash_out, out + n * 96, n * 96, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  return DH_OK;
+}
+
+int dh_msm_level0_shape_debug(uint64_t* rows_per_set, uint64_t* entries, int* half_a, int* half_b) {
+  if (!rows_per_set || !entries || !half_a || !half_b) return fail(DH_EINVAL, "null argument");
+  *rows_per_set = g_level0.rows;
+  *entries = g_level0.entries;
+  *half_a = g_level0.half_a;
+  *half_b = g_level0.half_b;
   return DH_OK;
 }
 

@@ -60,7 +60,7 @@ __global__ void k_msm_hist(const uint32_t* __restrict__ pidx, const uint32_t* __
   if (e >= m) return;
   const uint4 s = scal[sidx ? sidx[e] : pidx[e]];
   const size_t gi = entry_group(grp, e, g.gsize);
-  for (uint32_t h = 0; h < g.halves; h++) {
+  for (uint32_t h = 0; h < msm_keyed(g); h++) {
     const uint4 sh = half_scalar(s, h, g);
     uint32_t carry = 0;
     for (int w = 0; w < g.nwin; w++) {
@@ -78,7 +78,7 @@ __global__ void k_msm_scatter(const uint32_t* __restrict__ pidx, const uint32_t*
   const uint32_t idx0 = pidx[e];
   const uint4 s = scal[sidx ? sidx[e] : idx0];
   const size_t gi = entry_group(grp, e, g.gsize);
-  for (uint32_t h = 0; h < g.halves; h++) {
+  for (uint32_t h = 0; h < msm_keyed(g); h++) {
     const uint4 sh = half_scalar(s, h, g);
     const uint32_t idx = half_point(g, idx0, h);  // endo(P) sits half_stride points after P
     uint32_t carry = 0;
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(SORT_T) void k_msm_sort_lds(const uint32_t* __restr
   __syncthreads();
   // split rows: a slab inside one group's rows holds keys of the halves [h_lo, h_hi] only (at c = 16 a slab is about
   // one row), so the other half's digits are not recoded for it
-  uint32_t h_lo = 0, h_hi = g.halves - 1;
+  uint32_t h_lo = 0, h_hi = msm_keyed(g) - 1;
   if (g.split) {
     const size_t r0 = K0 / g.nbuck, r1 = (K0 + ns - 1) / g.nbuck, R = msm_rows(g);
     if (r0 / R == r1 / R) {
@@ -311,7 +311,7 @@ hipError_t launch_scan(const uint32_t* cnt, size_t nk, uint32_t* off, uint32_t* 
 
 hipError_t launch_msm_sort(const msm_geom& g, const uint32_t* pidx, const uint32_t* sidx, const uint32_t* grp, size_t m,
                            size_t ngroups, const uint4* scal, msm_ws& ws, hipStream_t st) {
-  if (g.split && g.halves != 2) return hipErrorInvalidValue;
+  if ((g.split && g.halves != 2) || (g.half0 && !g.split)) return hipErrorInvalidValue;
   size_t nk = ngroups * msm_rows(g) * (size_t)g.nbuck;
   ws.max_entries = msm_entries(g, m);
   hipError_t e = hipMemsetAsync(ws.cnt, 0, nk * sizeof(uint32_t), st);
@@ -1105,6 +1105,7 @@ static hipError_t msm28(const msm_geom& g, size_t ngroups, const uint32_t* S, co
                         const uint8_t* skip, int nsets = 2) {
   using CQ = typename prime_of<C>::T;  // the hash set's curve in a split-row launch
   if (g.split && (std::is_same<C, CQ>::value || nsets != 2 || g.halves != 2)) return hipErrorInvalidValue;
+  if (g.half0 && !g.split) return hipErrorInvalidValue;
   const size_t nk = ngroups * msm_rows(g) * (size_t)g.nbuck;
   constexpr size_t jw = 3 * C::EW;
   uint32_t* bB = ws.buckets + nk * jw;
@@ -1165,9 +1166,12 @@ static hipError_t msm28(const msm_geom& g, size_t ngroups, const uint32_t* S, co
   if constexpr (!std::is_same<C, CQ>::value) {
     if (g.split) {
       hipLaunchKernelGGL(k_msm_iso_rows28, dim3(nblk(rows, 64)), dim3(64), 0, st, const_cast<uint32_t*>(rowsum), rows, rows);
-      hipLaunchKernelGGL(k_msm_windows28_split<C>, dim3(nblk(2 * nsets * ngroups, 64)), dim3(64), 0, st, rowsum, g,
-                         (size_t)nsets * ngroups, ws.out2);
-      return hipGetLastError();
+      if (!g.half0) {
+        hipLaunchKernelGGL(k_msm_windows28_split<C>, dim3(nblk(2 * nsets * ngroups, 64)), dim3(64), 0, st, rowsum, g,
+                           (size_t)nsets * ngroups, ws.out2);
+        return hipGetLastError();
+      }
+      // one keyed half: both sets' rows are now plain E1 rows of one scalar, nwin per (set, group)
     }
   }
   hipLaunchKernelGGL(k_msm_windows28<C>, dim3(nblk(nsets * ngroups, 64)), dim3(64), 0, st, rowsum, g, nsets * ngroups, ws.out2);

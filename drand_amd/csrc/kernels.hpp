@@ -30,10 +30,16 @@ struct msm_geom {
   // nwin .. 2 nwin - 1 (k_msm_windows28_split). Each half is recoded on its own, as for split = 0. half_stride stays
   // the round count (the bucket pass's skip test).
   uint32_t split = 0;
+  // 1 (split = 1, the G1 level 0 on one scalar half): only half 0 of a scalar is keyed, the round's scalar
+  // is a alone. nwin window rows per group and nwin entries per point, the row sums are plain rows of one scalar
+  // (k_msm_windows28 after the hash rows' isogeny). halves stays 2: half_scalar and the 63-bit recoding are a half's.
+  uint32_t half0 = 0;
 };
-inline size_t msm_entries(const msm_geom& g, size_t m) { return m * (size_t)g.nwin * g.halves; }
+// halves of a scalar that key window rows
+__host__ __device__ inline uint32_t msm_keyed(const msm_geom& g) { return g.half0 ? 1u : g.halves; }
+inline size_t msm_entries(const msm_geom& g, size_t m) { return m * (size_t)g.nwin * msm_keyed(g); }
 // window rows (of nbuck keys) per group
-__host__ __device__ inline uint32_t msm_rows(const msm_geom& g) { return (uint32_t)g.nwin * (g.split ? g.halves : 1u); }
+__host__ __device__ inline uint32_t msm_rows(const msm_geom& g) { return (uint32_t)g.nwin * (g.split ? msm_keyed(g) : 1u); }
 
 // device workspace of one MSM level (sized by the caller from msm_geom)
 struct msm_ws {

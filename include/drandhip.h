@@ -555,6 +555,16 @@ int dh_g1_round_prep_late_debug(const uint8_t* us, const uint8_t* sigs, size_t n
                                 uint8_t* hash_out);
 
 /*
+ * Test entry: the shape of the last level-0 MSM that a local batch (dh_verify_batch and its kin, not a node batch) ran
+ * on the calling thread: the window rows per point set, the sorted-list entries, and whether the a-half and the b-half
+ * of the rounds' scalars keyed rows. A large G1-signature batch keys the a-halves alone (DRANDHIP_G1_RLC_HALF, the
+ * default): nwin rows, n x nwin entries, half_a = 1, half_b = 0; with the switch at 0, 2 nwin, 2 n x nwin, 1, 1.
+ * Zeros before the thread's first such batch. A call split over workers (DRANDHIP_SPLIT) records the chunks that ran on
+ * the calling thread.
+ */
+int dh_msm_level0_shape_debug(uint64_t* rows_per_set, uint64_t* entries, int* half_a, int* half_b);
+
+/*
  * Live kernel timing: when enabled, every device stage of the verification path is bracketed by HIP
  * events on the stream it is launched on; dh_profile_read writes a JSON object
  * {"stage": {"count": c, "total_ms": t}, ...} into buf (returns the full length). dh_profile resets.
