@@ -35,6 +35,7 @@
 #include "bolt.hpp"
 #include "bolt_write.hpp"
 #include "kernels.hpp"
+#include "rdjson.hpp"
 
 namespace {
 
@@ -2156,6 +2157,7 @@ int run_split(size_t n, F&& fn, uint64_t seed) {
 }  // namespace
 
 static void stores_shutdown();  // store handles, below
+static void archives_shutdown();  // archive handles, below
 
 extern "C" {
 
@@ -2166,6 +2168,7 @@ int dh_init(uint32_t device_mask) {
 
 void dh_shutdown(void) {
   stores_shutdown();  // store handles (dh_store_open_bolt) are invalidated; one inside a call when that call ends
+  archives_shutdown();  // and archive handles (dh_archive_open_ndjson)
   // idle workers are freed now; a worker leased by a call still running on another thread is retired and freed
   // when that call returns, so the call never touches freed memory
   std::lock_guard<std::mutex> lk(g_ctx.mu);
@@ -4312,6 +4315,335 @@ int dh_store_save_trimmed(dh_store* s, uint64_t first, uint64_t last, const uint
     n_unl += m.n_unl;
   }
   return DH_OK;
+}
+
+}  // extern "C"
+
+// ---- client.RandomData JSON-lines archives on the device: the records every HTTP relay serves
+// (client/random.go:5-10, hexjson), one per line. The image is uploaded once per open archive and indexed there
+// (k_archive.hip); a window's columns come out in the layout dh_verify_batch_device takes. Locking and lifetime as
+// dh_store.
+
+struct dh_archive {
+  std::mutex mu;
+  std::atomic<bool> retire{false};
+  bool dead = false;
+  uint64_t len = 0, nrec = 0;
+  uint64_t stat[7] = {0, 0, 0, 0, 0, 0, dh::ARCHIVE_TILE};
+  hipStream_t st = nullptr;
+  dbuf d_file, cnt, base, scan_tmp, line_off, line_len, chunks, d_stat;
+  // dh_archive_check / dh_archive_deferred: one window's columns
+  dbuf rounds, sigs, sig_lens, prevs, prev_lens, rands, rand_lens, defer, verdict, rand_out, status;
+  dbuf carry, carry_round, carry_len, carry_sig;  // the record before the window
+  std::vector<uint8_t> h_defer;
+  void release() {
+    for (dbuf* b : {&d_file, &cnt, &base, &scan_tmp, &line_off, &line_len, &chunks, &d_stat, &rounds, &sigs, &sig_lens, &prevs, &prev_lens,
+                    &rands, &rand_lens, &defer, &verdict, &rand_out, &status, &carry, &carry_round, &carry_len, &carry_sig})
+      b->release();
+    if (st) (void)hipStreamDestroy(st);
+    st = nullptr;
+    dead = true;
+  }
+};
+static std::vector<dh_archive*> g_archives;  // under g_stores_mu
+
+static void archives_shutdown() {
+  std::lock_guard<std::mutex> lk(g_stores_mu);
+  for (dh_archive* a : g_archives) {
+    if (a->mu.try_lock()) {
+      a->release();
+      a->mu.unlock();
+    } else {
+      a->retire = true;
+    }
+  }
+}
+
+// entered with a->mu held
+static int archive_enter(dh_archive* a) {
+  if (a->retire.exchange(false)) a->release();
+  if (a->dead) return fail(DH_EINVAL, "archive handle invalidated by dh_shutdown (dh_archive_close it and open again)");
+  HIP_TRY(hipSetDevice(g_ctx.device));
+  return DH_OK;
+}
+struct archive_guard {
+  dh_archive* a;
+  explicit archive_guard(dh_archive* x) : a(x) { a->mu.lock(); }
+  ~archive_guard() {
+    if (a->retire.exchange(false)) a->release();
+    a->mu.unlock();
+  }
+};
+
+constexpr size_t ARCHIVE_CALL_ROWS = (size_t)4096 * 4096 - 2;  // as one store call
+
+static int archive_open(dh_archive* a, const uint8_t* buf, size_t len) {
+  int rc = ensure_device();
+  if (rc) return rc;
+  a->len = len;
+  HIP_TRY(hipStreamCreateWithFlags(&a->st, hipStreamNonBlocking));
+  if (!len) return DH_OK;
+  {
+    prof_wall p("archive_upload");
+    HIP_TRY(a->d_file.ensure(len));
+    HIP_TRY(hipMemcpyAsync(a->d_file.p, buf, len, hipMemcpyHostToDevice, a->st));
+    HIP_TRY(hipStreamSynchronize(a->st));
+  }
+  const size_t ntiles = (len + dh::ARCHIVE_TILE - 1) / dh::ARCHIVE_TILE;
+  {
+    prof_wall p("archive_index");
+    HIP_TRY(a->cnt.ensure(ntiles * 4));
+    HIP_TRY(a->base.ensure((ntiles + 1) * 4));
+    HIP_TRY(a->scan_tmp.ensure((ntiles / 4096 + 2) * 4));
+    HIP_TRY(dh::launch_ndjson_count(a->d_file.as<uint8_t>(), len, ntiles, a->cnt.as<uint32_t>(), a->st));
+    HIP_TRY(dh::launch_scan(a->cnt.as<uint32_t>(), ntiles, a->base.as<uint32_t>(), a->scan_tmp.as<uint32_t>(), a->st));
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, a->base.as<uint32_t>() + ntiles, 4, hipMemcpyDeviceToHost, a->st));
+    HIP_TRY(hipStreamSynchronize(a->st));
+    a->nrec = total;
+    HIP_TRY(a->line_off.ensure((size_t)total * 8 + 8));
+    HIP_TRY(a->line_len.ensure((size_t)total * 4 + 4));
+    HIP_TRY(dh::launch_ndjson_index(a->d_file.as<uint8_t>(), len, ntiles, a->base.as<uint32_t>(), a->line_off.as<uint64_t>(),
+                                    a->line_len.as<uint32_t>(), a->st));
+    HIP_TRY(hipStreamSynchronize(a->st));
+  }
+  prof_wall p("archive_stat");
+  uint64_t st5[5];
+  HIP_TRY(a->chunks.ensure((a->nrec / 64 + 1) * sizeof(dh::archive_stat)));
+  HIP_TRY(a->d_stat.ensure(sizeof st5));
+  HIP_TRY(dh::launch_ndjson_stat(a->d_file.as<uint8_t>(), len, a->line_off.as<uint64_t>(), a->line_len.as<uint32_t>(), a->nrec, a->chunks.p,
+                                 a->d_stat.as<uint64_t>(), a->st));
+  HIP_TRY(hipMemcpyAsync(st5, a->d_stat.p, sizeof st5, hipMemcpyDeviceToHost, a->st));
+  HIP_TRY(hipStreamSynchronize(a->st));
+  a->stat[0] = a->nrec;
+  memcpy(a->stat + 1, st5, sizeof st5);
+  return DH_OK;
+}
+
+// records [first, first + n) of the archive into the columns; waits for the stream
+static int archive_gather(dh_archive* a, uint64_t first, size_t n, const dh::archive_cols& c) {
+  if (!n) return DH_OK;
+  timed_launches tl(a->st);  // resolved after the stream wait below
+  HIP_TRY(tl.run("k_ndjson_gather", [&] {
+    return dh::launch_ndjson_gather(a->d_file.as<uint8_t>(), a->len, a->line_off.as<uint64_t>() + first, a->line_len.as<uint32_t>() + first, n,
+                                    c, a->st);
+  }));
+  HIP_TRY(hipStreamSynchronize(a->st));
+  return DH_OK;
+}
+
+static void archive_clamp(const dh_archive* a, uint64_t first, size_t* n) {
+  if (first >= a->nrec) *n = 0;
+  else if (*n > a->nrec - first) *n = (size_t)(a->nrec - first);
+}
+
+extern "C" {
+
+int dh_archive_open_ndjson(const uint8_t* buf, size_t len, dh_archive** out) {
+  if (!out || (len && !buf)) return fail(DH_EINVAL, "null argument");
+  *out = nullptr;
+  if (len > store_max_bytes())
+    return fail(DH_ENOMEM, "archive of %zu bytes exceeds DRANDHIP_STORE_MAX_BYTES (%zu): keep the host reader", len, store_max_bytes());
+  if (len >> 33) return fail(DH_ENOMEM, "archive of %zu bytes: at most 8 GiB per handle (the record index is 32 bits wide): split it at a newline", len);
+  if (len && dh::bolt::rdjson_is_array(dh::bolt::view{buf, (uint64_t)len}))
+    return fail(DH_EINVAL, "the archive starts with '[': the JSON-array form is not framed on the device, keep the host reader");
+  dh_archive* a = new dh_archive();
+  int rc = archive_open(a, buf, len);
+  if (rc) {
+    a->release();
+    delete a;
+    return rc;
+  }
+  std::lock_guard<std::mutex> lk(g_stores_mu);
+  g_archives.push_back(a);
+  *out = a;
+  return DH_OK;
+}
+
+int dh_archive_stat(const dh_archive* a, uint64_t out[7]) {
+  if (!a || !out) return fail(DH_EINVAL, "null argument");
+  memcpy(out, a->stat, sizeof a->stat);  // fixed at open
+  return DH_OK;
+}
+
+void dh_archive_close(dh_archive* a) {
+  if (!a) return;
+  {
+    std::lock_guard<std::mutex> lk(g_stores_mu);
+    g_archives.erase(std::remove(g_archives.begin(), g_archives.end(), a), g_archives.end());
+  }
+  {
+    std::lock_guard<std::mutex> lk(a->mu);
+    if (!a->dead && hipSetDevice(g_ctx.device) == hipSuccess) a->release();
+  }
+  delete a;
+}
+
+int dh_archive_lines(dh_archive* a, uint64_t first_rec, size_t n_rec, uint64_t* off_out, uint32_t* len_out) {
+  if (!a) return fail(DH_EINVAL, "null argument");
+  archive_guard g(a);
+  int rc = archive_enter(a);
+  if (rc) return rc;
+  archive_clamp(a, first_rec, &n_rec);
+  if (!n_rec) return DH_OK;
+  if (!off_out || !len_out) return fail(DH_EINVAL, "null output");
+  HIP_TRY(hipMemcpy(off_out, a->line_off.as<uint64_t>() + first_rec, n_rec * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(len_out, a->line_len.as<uint32_t>() + first_rec, n_rec * 4, hipMemcpyDeviceToHost));
+  return DH_OK;
+}
+
+int dh_archive_deferred(dh_archive* a, uint64_t first_rec, size_t n_rec, uint64_t* idx_out, size_t cap, size_t* n_out) {
+  if (!a || !n_out || (cap && !idx_out)) return fail(DH_EINVAL, "null argument");
+  archive_guard g(a);
+  int rc = archive_enter(a);
+  if (rc) return rc;
+  *n_out = 0;
+  archive_clamp(a, first_rec, &n_rec);
+  if (!n_rec || !a->stat[1]) return DH_OK;
+  size_t n = 0;
+  const size_t win = (size_t)1 << 20;
+  for (size_t at = 0; at < n_rec; at += win) {
+    const size_t m = std::min(win, n_rec - at);
+    HIP_TRY(a->rounds.ensure(m * 8));
+    HIP_TRY(a->defer.ensure(m));
+    const dh::archive_cols c{a->rounds.as<uint64_t>(), a->defer.as<uint8_t>(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 4, 4};
+    if ((rc = archive_gather(a, first_rec + at, m, c))) return rc;
+    a->h_defer.resize(m);
+    HIP_TRY(hipMemcpy(a->h_defer.data(), a->defer.p, m, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < m; i++) {
+      if (!a->h_defer[i]) continue;
+      if (n < cap) idx_out[n] = first_rec + at + i;
+      n++;
+    }
+  }
+  *n_out = n;
+  if (n > cap) return fail(DH_EINVAL, "%zu deferred records, room for %zu", n, cap);
+  return DH_OK;
+}
+
+int dh_archive_beacons_device(dh_archive* a, uint64_t first_rec, size_t n_rec, size_t sig_stride, size_t prev_stride, uint64_t* d_rounds,
+                              uint8_t* d_sigs, uint32_t* d_sig_lens, uint8_t* d_prevs, uint32_t* d_prev_lens, uint8_t* d_rands,
+                              uint32_t* d_rand_lens, uint8_t* d_deferred, size_t* n_out, void* hip_stream) {
+  if (!a || !n_out) return fail(DH_EINVAL, "null argument");
+  const bool want_prev = d_prevs || d_prev_lens;
+  if (!sig_stride || (sig_stride & 3) || sig_stride > ((size_t)1 << 20) ||
+      (want_prev && (!prev_stride || (prev_stride & 3) || prev_stride > ((size_t)1 << 20))))
+    return fail(DH_EINVAL, "row strides %zu / %zu: positive multiples of 4, at most 1 MiB", sig_stride, prev_stride);
+  if (!d_prevs != !d_prev_lens) return fail(DH_EINVAL, "d_prevs and d_prev_lens are given together or not at all");
+  if (!d_rands != !d_rand_lens) return fail(DH_EINVAL, "d_rands and d_rand_lens are given together or not at all");
+  archive_guard g(a);
+  int rc = archive_enter(a);
+  if (rc) return rc;
+  prof_wall p("archive_gather");
+  if (hip_stream) HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));  // the output buffers may be in use there
+  archive_clamp(a, first_rec, &n_rec);
+  *n_out = n_rec;
+  if (n_rec > ARCHIVE_CALL_ROWS) return fail(DH_EINVAL, "window of %zu records: at most 16M records per call", n_rec);
+  if (n_rec && (!d_rounds || !d_sigs || !d_sig_lens || !d_deferred)) return fail(DH_EINVAL, "null output");
+  const dh::archive_cols c{d_rounds, d_deferred, d_sigs, d_sig_lens, d_prevs, d_prev_lens, d_rands, d_rand_lens, (uint32_t)sig_stride,
+                           (uint32_t)(want_prev ? prev_stride : 4)};
+  return archive_gather(a, first_rec, n_rec, c);
+}
+
+int dh_archive_check(dh_archive* a, int scheme, const uint8_t* pk, size_t pk_len, uint64_t first_rec, size_t n_rec,
+                     const uint64_t* anchor_round, const uint8_t* anchor_sig, size_t anchor_sig_len, size_t window, uint64_t seed,
+                     uint8_t* status_out, uint64_t counts_out[6]) {
+  if (!a || !pk || !counts_out) return fail(DH_EINVAL, "null argument");
+  if (scheme < 0 || scheme > 3) return fail(DH_EINVAL, "unknown scheme %d", scheme);
+  if (!window) return fail(DH_EINVAL, "window must be >= 1");
+  if (anchor_round && anchor_sig_len && !anchor_sig) return fail(DH_EINVAL, "null anchor signature");
+  const uint32_t sig_len = (uint32_t)dh_sig_len(scheme);
+  const bool chained = scheme == DH_SCHEME_CHAINED;
+  archive_guard g(a);
+  int rc = archive_enter(a);
+  if (rc) return rc;
+  memset(counts_out, 0, 6 * sizeof(uint64_t));
+  archive_clamp(a, first_rec, &n_rec);
+  if (!n_rec) return DH_OK;
+  if (!status_out) return fail(DH_EINVAL, "null output");
+  window = std::min(window, ARCHIVE_CALL_ROWS);
+  const bool use_anchor = first_rec == 0 && anchor_round;
+  const uint64_t longest = std::max<uint64_t>(std::max<uint64_t>(sig_len, a->stat[3]),
+                                              std::max<uint64_t>(chained ? a->stat[4] : 0, use_anchor ? anchor_sig_len : 0));
+  const size_t stride = ((size_t)longest + 3) & ~(size_t)3;
+  if (stride > 65536)
+    return fail(DH_EINVAL, "row stride %zu above 64 KiB (a %llu-byte field): keep the host reader", stride, (unsigned long long)longest);
+  HIP_TRY(a->carry.ensure(8));
+  HIP_TRY(a->carry_round.ensure(8));
+  HIP_TRY(a->carry_len.ensure(8));
+  HIP_TRY(a->carry_sig.ensure(stride));
+  const size_t wmax = std::min(window, n_rec);
+  HIP_TRY(a->rounds.ensure(wmax * 8));
+  HIP_TRY(a->sigs.ensure(wmax * stride));
+  HIP_TRY(a->sig_lens.ensure(wmax * 4));
+  if (chained) {
+    HIP_TRY(a->prevs.ensure(wmax * stride));
+    HIP_TRY(a->prev_lens.ensure(wmax * 4));
+  }
+  HIP_TRY(a->rands.ensure(wmax * 32));
+  HIP_TRY(a->rand_lens.ensure(wmax * 4));
+  HIP_TRY(a->defer.ensure(wmax));
+  HIP_TRY(a->verdict.ensure(wmax));
+  HIP_TRY(a->rand_out.ensure(wmax * 32));
+  HIP_TRY(a->status.ensure(wmax));
+  const dh::archive_cols c{a->rounds.as<uint64_t>(), a->defer.as<uint8_t>(), a->sigs.as<uint8_t>(), a->sig_lens.as<uint32_t>(),
+                           chained ? a->prevs.as<uint8_t>() : nullptr, chained ? a->prev_lens.as<uint32_t>() : nullptr,
+                           a->rands.as<uint8_t>(), a->rand_lens.as<uint32_t>(), (uint32_t)stride, (uint32_t)stride};
+  // row `last` of the window's columns becomes the carried predecessor (stream order: before the next gather)
+  auto carry_row = [&](size_t last) -> int {
+    HIP_TRY(hipMemsetAsync(a->carry.p, 1, 1, a->st));
+    HIP_TRY(hipMemcpyAsync(a->carry.as<uint8_t>() + 1, a->defer.as<uint8_t>() + last, 1, hipMemcpyDeviceToDevice, a->st));
+    HIP_TRY(hipMemcpyAsync(a->carry_round.p, a->rounds.as<uint64_t>() + last, 8, hipMemcpyDeviceToDevice, a->st));
+    HIP_TRY(hipMemcpyAsync(a->carry_len.p, a->sig_lens.as<uint32_t>() + last, 4, hipMemcpyDeviceToDevice, a->st));
+    HIP_TRY(hipMemcpyAsync(a->carry_sig.p, a->sigs.as<uint8_t>() + last * stride, stride, hipMemcpyDeviceToDevice, a->st));
+    return DH_OK;
+  };
+  HIP_TRY(hipMemsetAsync(a->carry.p, 0, 8, a->st));
+  if (first_rec > 0) {  // the predecessor of the first record checked is the archive's record before it
+    if ((rc = archive_gather(a, first_rec - 1, 1, c)) || (rc = carry_row(0))) return rc;
+  } else if (use_anchor) {
+    const uint32_t al = (uint32_t)anchor_sig_len;
+    HIP_TRY(hipMemsetAsync(a->carry.p, 1, 1, a->st));
+    HIP_TRY(hipMemsetAsync(a->carry_sig.p, 0, stride, a->st));
+    HIP_TRY(hipMemcpyAsync(a->carry_round.p, anchor_round, 8, hipMemcpyHostToDevice, a->st));
+    HIP_TRY(hipMemcpyAsync(a->carry_len.p, &al, 4, hipMemcpyHostToDevice, a->st));
+    if (al) HIP_TRY(hipMemcpyAsync(a->carry_sig.p, anchor_sig, al, hipMemcpyHostToDevice, a->st));
+    HIP_TRY(hipStreamSynchronize(a->st));  // `al` is on this frame
+  }
+  for (size_t at = 0; at < n_rec; at += window) {
+    const size_t m = std::min(window, n_rec - at);
+    {
+      prof_wall p("archive_gather");
+      if ((rc = archive_gather(a, first_rec + at, m, c))) return rc;
+    }
+    {
+      prof_wall p("archive_verify");
+      // a deferred row is verified as the all-zero record it was left as, and its verdict is not read; the chained
+      // scheme verifies each record against its OWN previous_signature (client/verify.go:171-199, non-strict)
+      rc = dh_verify_batch_device(scheme, pk, pk_len, a->rounds.as<uint64_t>(), a->sigs.as<uint8_t>(), stride,
+                                  chained ? a->prevs.as<uint8_t>() : nullptr, stride, chained ? a->prev_lens.as<uint32_t>() : nullptr, m,
+                                  a->verdict.as<uint8_t>(), a->rand_out.as<uint8_t>(), seed, nullptr, nullptr);
+      if (rc) return rc;
+    }
+    prof_wall p("archive_fold");
+    const dh::archive_fold_in f{m, sig_len, chained ? 1u : 0u, (uint32_t)stride, (uint32_t)stride, a->verdict.as<uint8_t>(),
+                                a->rand_out.as<uint8_t>(), c.rounds, c.deferred, c.sigs, c.sig_lens, c.prevs, c.prev_lens, c.rands, c.rand_lens,
+                                a->carry.as<uint8_t>(), a->carry_round.as<uint64_t>(), a->carry_len.as<uint32_t>(), a->carry_sig.as<uint8_t>()};
+    HIP_TRY(dh::launch_archive_fold(f, a->status.as<uint8_t>(), a->st));
+    HIP_TRY(hipMemcpyAsync(status_out + at, a->status.p, m, hipMemcpyDeviceToHost, a->st));
+    if ((rc = carry_row(m - 1))) return rc;
+    HIP_TRY(hipStreamSynchronize(a->st));
+  }
+  for (size_t i = 0; i < n_rec; i++) {
+    const uint8_t s = status_out[i];
+    counts_out[1] += s & DH_AR_DEFERRED ? 1 : 0;
+    counts_out[2] += s & DH_AR_INVALID ? 1 : 0;
+    counts_out[3] += s & DH_AR_RANDOMNESS ? 1 : 0;
+    counts_out[4] += s & DH_AR_SEQUENCE ? 1 : 0;
+    counts_out[5] += s & DH_AR_LINK ? 1 : 0;
+  }
+  counts_out[0] = n_rec;
+  return counts_out[1] ? DH_DEFERRED : DH_OK;
 }
 
 }  // extern "C"

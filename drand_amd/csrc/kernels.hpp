@@ -318,6 +318,56 @@ hipError_t launch_bolt_gather_json(const uint8_t* file, const void* leaves, cons
 hipError_t launch_bolt_fold_json(const uint32_t* sig_lens, const uint8_t* deferred, const uint8_t* verdict, size_t n, uint32_t sig_len,
                                  uint8_t* bad, hipStream_t st);
 
+// client.RandomData JSON-lines archives (k_archive.hip). `file`: the image, 16-byte aligned. count: the
+// record starts per tile of ARCHIVE_TILE bytes (then launch_scan: base, ntiles + 1 words); index: line_off / line_len
+// per record in file order (a line above 4096 bytes: length 4097). stat: chunks = one archive_stat per 64 records
+// (scratch), out5 = {deferred, longest line, longest decoded signature / previous_signature / randomness}. gather:
+// records [0, n) of the line_off / line_len handed in, one row each; sigs / sig_lens, prevs / prev_lens and rands /
+// rand_lens are nullable in pairs, strides multiples of 4, rands rows are 32 bytes. fold: dh_archive_check's status byte per row.
+constexpr uint32_t ARCHIVE_TILE = 4096;
+struct archive_stat {
+  uint32_t n_deferred, max_line, max_sig, max_prev, max_rand, pad;
+};
+struct archive_cols {
+  uint64_t* rounds;
+  uint8_t* deferred;
+  uint8_t* sigs;
+  uint32_t* sig_lens;
+  uint8_t* prevs;
+  uint32_t* prev_lens;
+  uint8_t* rands;
+  uint32_t* rand_lens;
+  uint32_t sig_stride, prev_stride;
+};
+enum : uint32_t { AR_DEFERRED = 1, AR_NO_SIGNATURE = 2, AR_INVALID = 4, AR_RANDOMNESS = 8, AR_SEQUENCE = 16, AR_LINK = 32, AR_PRED_DEFERRED = 64 };
+struct archive_fold_in {
+  size_t n;
+  uint32_t want_sig_len, chained, sig_stride, prev_stride;
+  const uint8_t* verdict;
+  const uint8_t* rand_out;  // 32 bytes per row: SHA-256 of the row's first want_sig_len bytes
+  const uint64_t* rounds;
+  const uint8_t* deferred;
+  const uint8_t* sigs;
+  const uint32_t* sig_lens;
+  const uint8_t* prevs;  // chained only
+  const uint32_t* prev_lens;
+  const uint8_t* rands;
+  const uint32_t* rand_lens;
+  // the record before row 0: carry = {there is one, it is deferred}, its round, signature length and signature row
+  const uint8_t* carry;
+  const uint64_t* carry_round;
+  const uint32_t* carry_len;
+  const uint8_t* carry_sig;
+};
+hipError_t launch_ndjson_count(const uint8_t* file, uint64_t len, size_t ntiles, uint32_t* cnt, hipStream_t st);
+hipError_t launch_ndjson_index(const uint8_t* file, uint64_t len, size_t ntiles, const uint32_t* base, uint64_t* line_off, uint32_t* line_len,
+                               hipStream_t st);
+hipError_t launch_ndjson_stat(const uint8_t* file, uint64_t len, const uint64_t* line_off, const uint32_t* line_len, size_t n, void* chunks,
+                              uint64_t* out5, hipStream_t st);
+hipError_t launch_ndjson_gather(const uint8_t* file, uint64_t len, const uint64_t* line_off, const uint32_t* line_len, size_t n,
+                                const archive_cols& c, hipStream_t st);
+hipError_t launch_archive_fold(const archive_fold_in& f, uint8_t* status, hipStream_t st);
+
 // verifier columns -> the leaf pages of a trimmed bbolt store (k_bolt_write.hip). need: the record
 // sizes 24 + lens[i] (then launch_scan), err_word set when rounds do not ascend or a length passes the stride. pack:
 // leaves = boltw::leaf_desc records (24 B, one wave each); `image` starts at page 4 and holds every leaf extent;

@@ -17,6 +17,9 @@ store file, plus columns(first, last) for bulk ingestion.
   with BoltUntrimmedStore; records that are not canonical hexjson are decoded here, by beacon_from_hexjson.
 * hexjson records: client.RandomData {"round","randomness","signature","previous_signature"}
   (/root/reference/client/random.go:5-25) and BeaconPacket-shaped JSON, one object per line or a JSON list.
+* DeviceArchive — an archive of such records, one per line, parsed and checked on the device (libdrandhip
+  dh_archive_*), with check_random_data_host as the serial host form of the same check and
+  archive_to_trimmed_store writing a checked archive as a trimmed store file.
 """
 import ctypes
 import json
@@ -892,3 +895,331 @@ def random_data_columns(records, sig_len):
         if len(r["signature"]) == sig_len:
             sigs[i] = np.frombuffer(r["signature"], np.uint8)
     return rounds, sigs, [r["previous_signature"] for r in records], [r["randomness"] for r in records]
+
+
+# ---- client.RandomData JSON-lines archives
+
+_U64 = (1 << 64) - 1
+AR_DEFERRED, AR_NO_SIGNATURE, AR_INVALID, AR_RANDOMNESS = (_lib.DH_AR_DEFERRED, _lib.DH_AR_NO_SIGNATURE, _lib.DH_AR_INVALID,
+                                                          _lib.DH_AR_RANDOMNESS)
+AR_SEQUENCE, AR_LINK, AR_PRED_DEFERRED = _lib.DH_AR_SEQUENCE, _lib.DH_AR_LINK, _lib.DH_AR_PRED_DEFERRED
+_RD_FIELDS = ("randomness", "signature", "previous_signature")
+
+
+def random_data_from_line(line):
+    """ONE client.RandomData record (one line of an archive, bytes or str) -> {round, randomness, signature,
+    previous_signature} as read_random_data gives it: json.loads plus that function's field rules, with the round
+    held to 64 bits. None for a whitespace-only line; raises one of DECODE_ERRORS for text that does not decode.
+    This is the project's restatement of the record's JSON rules, not a decoder pinned to nikkolasg/hexjson: it decides
+    the records the device defers."""
+    text = bytes(line).decode("utf-8") if not isinstance(line, str) else line
+    if not text.strip():
+        return None
+    o = json.loads(text)
+    rnd = int(o.get("round", 0))
+    if not 0 <= rnd <= _U64:
+        raise ValueError("round %d does not fit 64 bits" % rnd)
+    return {"round": rnd, "randomness": _hexbytes(o.get("randomness")), "signature": _hexbytes(o.get("signature")),
+            "previous_signature": _hexbytes(o.get("previous_signature"))}
+
+
+def random_data_line(rec):
+    """The hexjson form the relays write (cmd/relay-s3/main.go:127-141 through nikkolasg/hexjson): the fields in the
+    order of client/random.go:5-10, lowercase hex, omitempty; bytes without a newline."""
+    parts = []
+    if int(rec.get("round", 0)):
+        parts.append(b'"round":%d' % int(rec["round"]))
+    for k in _RD_FIELDS:
+        v = rec.get(k)
+        if v:
+            parts.append(b'"%s":"%s"' % (k.encode(), bytes(v).hex().encode()))
+    return b"{" + b",".join(parts) + b"}"
+
+
+def archive_lines(data):
+    """The framing of an archive: the non-empty runs of bytes between b"\\n" bytes, in file order."""
+    return [l for l in bytes(data).split(b"\n") if l]
+
+
+def _verify_records(scheme, pubkey, recs, seed=0):
+    """[bool] for records whose signature has the scheme's length: one verify_beacons call, the chained scheme against
+    each record's own previous_signature."""
+    if not recs:
+        return []
+    rounds = np.array([r["round"] for r in recs], dtype=np.uint64)
+    sigs = np.array([np.frombuffer(r["signature"], np.uint8) for r in recs], dtype=np.uint8).reshape(len(recs), scheme.sig_len)
+    prevs = [r["previous_signature"] for r in recs] if scheme.chained else None
+    ok, _ = scheme.verify_beacons(pubkey, rounds, sigs, prevs, seed=seed, want_randomness=False)
+    return [bool(v) for v in ok]
+
+
+def _own_bits(rec, sig_len, verdict):
+    """Bits 2 / 4 / 8 of a decoded record; verdict: the verifier's, read only for a signature of the scheme's length."""
+    import hashlib
+    sig = rec["signature"]
+    st = 0
+    if not sig:
+        st |= AR_NO_SIGNATURE | AR_INVALID
+    elif len(sig) != sig_len or not verdict:
+        st |= AR_INVALID
+    if rec["randomness"] and rec["randomness"] != hashlib.sha256(sig).digest():
+        st |= AR_RANDOMNESS
+    return st
+
+
+def _pred_bits(rec, pred, chained):
+    """Bits 16 / 32 of a decoded record against its predecessor {round, signature} (None: it has none)."""
+    st = 0
+    if pred is not None:
+        if rec["round"] != (pred["round"] + 1) & _U64:
+            st |= AR_SEQUENCE
+        if chained and rec["previous_signature"] != pred["signature"]:
+            st |= AR_LINK
+    return st
+
+
+def _anchor_rec(anchor):
+    if anchor is None:
+        return None
+    rnd, sig = anchor
+    return {"round": int(rnd), "signature": bytes(sig)}
+
+
+def check_random_data_host(lines, scheme, pubkey, anchor=None, verify=None):
+    """The serial host check of an archive, the yardstick of DeviceArchive.check: one status byte (the DH_AR_* bits of
+    include/drandhip.h, bits 1 and 64 never set) per record, as a numpy uint8 array. lines: the archive's bytes, or its
+    lines already framed. Each line goes through random_data_from_line: a whitespace-only line is dropped from the
+    result; one that does not decode gets DH_AR_INVALID and, having neither round nor signature, is no predecessor:
+    the record after it is compared with the last record that decoded (the anchor (round, signature) before the first).
+    verify(scheme, pubkey, records) -> [bool] replaces the device verifier (the CPU tests pass the oracle)."""
+    if isinstance(lines, (bytes, bytearray, memoryview)):
+        lines = archive_lines(lines)
+    verify = verify or _verify_records
+    recs = []
+    for l in lines:
+        try:
+            r = random_data_from_line(l)
+        except DECODE_ERRORS:
+            r = False
+        if r is not None:
+            recs.append(r)
+    todo = [r for r in recs if r and len(r["signature"]) == scheme.sig_len]
+    verdict = dict(zip(map(id, todo), verify(scheme, pubkey, todo)))
+    out = np.zeros(len(recs), np.uint8)
+    pred = _anchor_rec(anchor)
+    for i, r in enumerate(recs):
+        if r is False:
+            out[i] = AR_INVALID
+            continue
+        out[i] = _own_bits(r, scheme.sig_len, verdict.get(id(r), False)) | _pred_bits(r, pred, scheme.chained)
+        pred = r
+    return out
+
+
+class DeviceArchive:
+    """A client.RandomData JSON-lines archive parsed on the device (dh_archive_*): the image is uploaded
+    and indexed once; beacons_device gives a window's columns as torch tensors in the layout dh_verify_batch_device and
+    BoltWriter.append take; check verifies every record and resolves the records the device defers here, through
+    random_data_from_line. A context manager. The JSON-array form raises ValueError: read_random_data reads it."""
+
+    STAT = ("records", "deferred", "longest_line", "longest_signature", "longest_previous", "longest_randomness", "tile_bytes")
+
+    def __init__(self, path_or_bytes):
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            self._data = bytes(path_or_bytes)
+        else:
+            with open(path_or_bytes, "rb") as f:
+                self._data = f.read()
+        self._h = None
+        self._resolved = {}
+        lib = _lib.load()
+        h = ctypes.c_void_p()
+        DeviceBoltStore._raise(lib.dh_archive_open_ndjson(self._data, len(self._data), ctypes.byref(h)))
+        self._h = h
+        st = (ctypes.c_uint64 * 7)()
+        DeviceBoltStore._raise(lib.dh_archive_stat(h, st))
+        self._stat = [int(x) for x in st]
+
+    def close(self):
+        if self._h is not None:
+            _lib.load().dh_archive_close(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001 - interpreter shutdown
+            pass
+
+    def __len__(self):
+        return self._stat[0]
+
+    def stat(self):
+        return dict(zip(self.STAT, self._stat))
+
+    def _window(self, first, n):
+        first = int(first)
+        n = max(0, len(self) - first) if n is None else int(n)
+        return first, max(0, min(n, len(self) - first))
+
+    def lines(self, first=0, n=None):
+        """(byte offsets uint64[n], lengths uint32[n]) of records first .. first + n - 1; a line above 4096 bytes has
+        length 4097."""
+        first, n = self._window(first, n)
+        off, ln = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+        DeviceBoltStore._raise(_lib.load().dh_archive_lines(self._h, first, n, ctypes.c_void_p(off.ctypes.data),
+                                                            ctypes.c_void_p(ln.ctypes.data)))
+        return off, ln
+
+    def line(self, i):
+        """The bytes of record i, from the host copy (whatever its length)."""
+        off, _ = self.lines(i, 1)
+        if not len(off):
+            raise IndexError(i)
+        end = self._data.find(b"\n", int(off[0]))
+        return self._data[int(off[0]):end if end >= 0 else len(self._data)]
+
+    def deferred(self, first=0, n=None):
+        """Indices of the records the device leaves to the host decoder, ascending."""
+        first, n = self._window(first, n)
+        cap = max(1, self._stat[1])
+        out = np.zeros(cap, np.uint64)
+        k = ctypes.c_size_t(0)
+        DeviceBoltStore._raise(_lib.load().dh_archive_deferred(self._h, first, n, ctypes.c_void_p(out.ctypes.data), cap, ctypes.byref(k)))
+        return [int(x) for x in out[:k.value]]
+
+    def default_stride(self, sig_len=0):
+        return max(4, (max(int(sig_len), self._stat[3]) + 3) & ~3)
+
+    def beacons_device(self, first=0, n=None, sig_stride=None, prev_stride=None, want_prev=True, want_rand=True):
+        """Records first .. first + n - 1 in device memory: (rounds int64[n] (the u64 bit pattern), sigs uint8[n,
+        sig_stride], sig_lens int32[n], prevs uint8[n, prev_stride] | None, prev_lens int32[n] | None, rands uint8[n, 32]
+        | None, rand_lens int32[n] | None, deferred uint8[n]). Strides default to the archive's longest decoded field
+        rounded up to 4. A value longer than its stride leaves a zero row and its true length; a deferred record is all
+        zero."""
+        import torch
+        first, n = self._window(first, n)
+        sig_stride = int(sig_stride or self.default_stride())
+        prev_stride = int(prev_stride or max(4, (self._stat[4] + 3) & ~3))
+        dev = torch.device("cuda")
+        rounds = torch.empty(n, dtype=torch.int64, device=dev)
+        sigs = torch.empty((n, sig_stride), dtype=torch.uint8, device=dev)
+        sig_lens = torch.empty(n, dtype=torch.int32, device=dev)
+        prevs = torch.empty((n, prev_stride), dtype=torch.uint8, device=dev) if want_prev else None
+        prev_lens = torch.empty(n, dtype=torch.int32, device=dev) if want_prev else None
+        rands = torch.empty((n, 32), dtype=torch.uint8, device=dev) if want_rand else None
+        rand_lens = torch.empty(n, dtype=torch.int32, device=dev) if want_rand else None
+        deferred = torch.empty(n, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        ptr = lambda t: (t.data_ptr() or None) if t is not None else None  # noqa: E731
+        k = ctypes.c_size_t(0)
+        DeviceBoltStore._raise(_lib.load().dh_archive_beacons_device(
+            self._h, first, n, sig_stride, prev_stride, ptr(rounds), ptr(sigs), ptr(sig_lens), ptr(prevs), ptr(prev_lens), ptr(rands),
+            ptr(rand_lens), ptr(deferred), ctypes.byref(k), None))
+        return rounds, sigs, sig_lens, prevs, prev_lens, rands, rand_lens, deferred
+
+    def check_device(self, scheme, pubkey, anchor=None, window=1 << 20, seed=0):
+        """dh_archive_check over the whole archive: (status uint8[records] with the deferred records marked
+        DH_AR_DEFERRED and undecided, counts dict)."""
+        n = len(self)
+        status = np.zeros(n, np.uint8)
+        counts = (ctypes.c_uint64 * 6)()
+        a = _anchor_rec(anchor)
+        ar = ctypes.c_uint64(a["round"]) if a else None
+        rc = _lib.load().dh_archive_check(self._h, scheme.id, bytes(pubkey), len(pubkey), 0, n, ctypes.byref(ar) if a else None,
+                                          a["signature"] if a else None, len(a["signature"]) if a else 0, int(window), int(seed),
+                                          ctypes.c_void_p(status.ctypes.data), counts)
+        if rc == _lib.DH_EINVAL and "64 KiB" in _lib.last_error():
+            raise StrideTooLarge(_lib.last_error())
+        DeviceBoltStore._raise(rc)
+        return status, dict(zip(("checked", "deferred", "invalid", "randomness", "sequence", "link"), [int(x) for x in counts]))
+
+    def resolve(self, i):
+        """Record i through the host decoder: a dict, None (whitespace only) or False (it does not decode); cached."""
+        if i not in self._resolved:
+            try:
+                self._resolved[i] = random_data_from_line(self.line(i))
+            except DECODE_ERRORS:
+                self._resolved[i] = False
+        return self._resolved[i]
+
+    def check(self, scheme, pubkey, anchor=None, window=1 << 20, seed=0):
+        """One status byte per record (numpy uint8; the DH_AR_* bits), equal to check_random_data_host over the same
+        bytes. The device decides the canonical records; each deferred line is decided HERE, by random_data_from_line (this
+        module's restatement, not a decoder pinned to nikkolasg/hexjson): a whitespace-only line is dropped from the
+        result, one that does not decode gets DH_AR_INVALID, a decoded one is verified in one small verify_beacons call,
+        and the predecessor bits are computed for it and for the record after it."""
+        status, _ = self.check_device(scheme, pubkey, anchor, window, seed)
+        todo = [int(i) for i in np.flatnonzero(status & (AR_DEFERRED | AR_PRED_DEFERRED))]
+        if not todo:
+            return status
+        dec = {i: self.resolve(i) for i in todo if status[i] & AR_DEFERRED}
+        ver = [r for r in dec.values() if r and len(r["signature"]) == scheme.sig_len]
+        verdict = dict(zip(map(id, ver), _verify_records(scheme, pubkey, ver, seed)))
+
+        def pred_of(i):  # the last record before i that decoded
+            j = i - 1
+            while j >= 0 and status[j] & AR_DEFERRED and not dec[j]:
+                j -= 1
+            return _anchor_rec(anchor) if j < 0 else (dec[j] if j in dec else self.resolve(j))
+
+        out = status.copy()
+        for i in todo:
+            if status[i] & AR_DEFERRED:
+                r = dec[i]
+                out[i] = AR_INVALID if not r else _own_bits(r, scheme.sig_len, verdict.get(id(r), False)) | _pred_bits(r, pred_of(i), scheme.chained)
+            else:  # canonical, behind a deferred record
+                out[i] = (int(status[i]) & ~AR_PRED_DEFERRED) | _pred_bits(self.resolve(i), pred_of(i), scheme.chained)
+        keep = np.ones(len(out), bool)
+        keep[[i for i, r in dec.items() if r is None]] = False
+        return out[keep]
+
+
+def archive_to_trimmed_store(archive, path, scheme, pubkey, anchor=None, window=STREAM_WINDOW, page_size=4096):
+    """A RandomData archive -> a trimmed store file at `path` (the bulk form of appendStore / schemeStore Put,
+    chain/beacon/store.go:55-77,99-124): DeviceArchive.check first, and a ValueError naming the first records when any
+    bit but DH_AR_RANDOMNESS is set (the reference overwrites randomness, client/verify.go:197); then the windows' rounds
+    / sigs / sig_lens columns go from the device into a BoltWriter (path + ".tmp", then os.replace). The file is byte for
+    byte write_trimmed_bolt of the same rows. archive: a DeviceArchive, a path or the bytes. Returns BoltWriter.finish()'s
+    dict."""
+    import torch
+    own = not isinstance(archive, DeviceArchive)
+    ar = DeviceArchive(archive) if own else archive
+    try:
+        status = ar.check(scheme, pubkey, anchor=anchor, window=window)
+        bad = np.flatnonzero(status & ~np.uint8(AR_RANDOMNESS))
+        if len(bad):
+            raise ValueError("%d of %d records do not pass: %s%s" % (len(bad), len(status), ", ".join(
+                "#%d (status %d)" % (int(i), int(status[i])) for i in bad[:8]), ", ..." if len(bad) > 8 else ""))
+        if not len(status):
+            raise NoBeaconStored("the archive holds no record")
+        window = max(1, min(int(window), MAX_CALL_ROWS))
+        stride = max(4, (scheme.sig_len + 3) & ~3)
+        with BoltWriter(path, page_size) as w:
+            for at in range(0, len(ar), window):
+                rounds, sigs, sig_lens, _p, _pl, _r, _rl, deferred = ar.beacons_device(at, window, sig_stride=stride, want_prev=False,
+                                                                                       want_rand=False)
+                idx = torch.nonzero(deferred).reshape(-1).cpu().tolist()
+                if idx:  # decided by the host decoder in check(): patch the rows in, leave the blank lines out
+                    keep = torch.ones(len(deferred), dtype=torch.bool, device=deferred.device)
+                    for i in idx:
+                        r = ar.resolve(at + i)
+                        if r is None:
+                            keep[i] = False
+                            continue
+                        rounds[i] = r["round"] - (1 << 64) if r["round"] >> 63 else r["round"]
+                        sigs[i, :len(r["signature"])] = torch.frombuffer(bytearray(r["signature"]), dtype=torch.uint8).to(sigs.device)
+                        sig_lens[i] = len(r["signature"])
+                    rounds, sigs, sig_lens = rounds[keep], sigs[keep].contiguous(), sig_lens[keep]
+                if len(rounds):
+                    w.append(rounds, sigs, sig_lens)
+            return w.finish()
+    finally:
+        if own:
+            ar.close()

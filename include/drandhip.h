@@ -565,6 +565,64 @@ int dh_g1_round_prep_late_debug(const uint8_t* us, const uint8_t* sigs, size_t n
 int dh_msm_level0_shape_debug(uint64_t* rows_per_set, uint64_t* entries, int* half_a, int* half_b);
 
 /*
+ * client.RandomData JSON-lines archives on the device: the records the HTTP relays serve
+ * (client/random.go:5-10, marshalled through hexjson), one per line:
+ *   {"round":367,"randomness":"<64 hex>","signature":"<96|192 hex>","previous_signature":"<192 hex>"}
+ * Framing: records are the maximal runs of bytes between '\n' bytes; a last run without a closing '\n' is a record when
+ * it is not empty; empty runs are skipped; record index = 0-based ordinal of the non-empty run. A buffer whose first
+ * byte outside '\n' is '[' (the JSON-array form) is DH_EINVAL: the caller keeps the host reader.
+ * Canonical records are decoded on the device: exactly '{' fields '}', the fields a subsequence of "round":D,
+ * "randomness":"H", "signature":"H", "previous_signature":"H" in that order joined by single commas ({} is canonical);
+ * D = 1-20 digits, no leading zero, not 0, below 2^64; H = a non-zero even number of characters 0-9a-f. Every other
+ * record (and every line above 4096 bytes) is DEFERRED: the device reports its index and decides nothing; the caller's
+ * host decoder does.
+ *
+ * dh_archive_open_ndjson: uploads buf[0, len) (never read outside it), indexes it. The image stays resident until
+ * close. Above DRANDHIP_STORE_MAX_BYTES (or 8 GiB): DH_ENOMEM. An empty buffer or one of '\n' bytes only opens with
+ * 0 records. A mutex in the handle serialises calls on it; dh_shutdown invalidates it (every call but close DH_EINVAL).
+ * dh_archive_stat: {records, deferred, longest line (4097 for every longer one), longest decoded signature, longest
+ * previous_signature, longest randomness, tile bytes of the index kernels}.
+ * dh_archive_lines: byte offset and length of records first_rec .. first_rec + n_rec - 1 into HOST arrays; n_rec is
+ * clamped to the archive here and below.
+ * dh_archive_deferred: the indices of the deferred records among them, ascending; more than cap: DH_EINVAL with *n_out
+ * = the number.
+ * dh_archive_beacons_device: the records' columns in DEVICE memory, in the layout dh_verify_batch_device and
+ * dh_bolt_writer_append_device take: rounds, signature rows of sig_stride bytes with their lengths, previous_signature
+ * rows (d_prevs / d_prev_lens nullable together), randomness rows of 32 bytes (d_rands / d_rand_lens nullable
+ * together), deferred flags. A value that fits its stride is copied whole and zero-padded; otherwise its row is all
+ * zero, never a prefix, and the length is still the true one. A deferred record: zero rows, zero lengths, round 0.
+ * Strides: positive multiples of 4, at most 1 MiB; at most 16M records per call. *n_out = the rows written.
+ * dh_archive_check: verifies the records `window` at a time and writes one status byte per record (HOST memory):
+ */
+#define DH_AR_DEFERRED 1       /* not canonical: no other bit is set, the call returns DH_DEFERRED */
+#define DH_AR_NO_SIGNATURE 2   /* decoded signature length 0 */
+#define DH_AR_INVALID 4        /* signature length != dh_sig_len(scheme), or the verifier rejects the record */
+#define DH_AR_RANDOMNESS 8     /* randomness present and not SHA-256(signature); informational */
+#define DH_AR_SEQUENCE 16      /* round != the predecessor's round + 1 */
+#define DH_AR_LINK 32          /* chained scheme: previous_signature != the predecessor's signature */
+#define DH_AR_PRED_DEFERRED 64 /* the predecessor is deferred: bits 16 and 32 are left 0 for the caller to decide */
+/*
+ * The chained scheme verifies each record against its OWN previous_signature. The predecessor of record i is record
+ * i - 1 of the archive, across windows; the predecessor of record 0 is the anchor {*anchor_round, anchor_sig} when
+ * anchor_round is not NULL, else record 0 has none (bits 16 / 32 / 64 clear). Rows are roundup4(max(dh_sig_len, the
+ * longest decoded value)) bytes; above 64 KiB: DH_EINVAL. counts_out = {records checked, deferred, invalid,
+ * randomness mismatches, sequence breaks, link breaks}. dh_profile stages: archive_upload, archive_index,
+ * archive_stat at open; archive_gather, archive_verify, archive_fold per window.
+ */
+typedef struct dh_archive dh_archive;
+int dh_archive_open_ndjson(const uint8_t* buf, size_t len, dh_archive** out);
+int dh_archive_stat(const dh_archive* archive, uint64_t out[7]);
+int dh_archive_lines(dh_archive* archive, uint64_t first_rec, size_t n_rec, uint64_t* off_out, uint32_t* len_out);
+int dh_archive_deferred(dh_archive* archive, uint64_t first_rec, size_t n_rec, uint64_t* idx_out, size_t cap, size_t* n_out);
+int dh_archive_beacons_device(dh_archive* archive, uint64_t first_rec, size_t n_rec, size_t sig_stride, size_t prev_stride,
+                              uint64_t* d_rounds, uint8_t* d_sigs, uint32_t* d_sig_lens, uint8_t* d_prevs, uint32_t* d_prev_lens,
+                              uint8_t* d_rands, uint32_t* d_rand_lens, uint8_t* d_deferred, size_t* n_out, void* hip_stream);
+int dh_archive_check(dh_archive* archive, int scheme, const uint8_t* pk, size_t pk_len, uint64_t first_rec, size_t n_rec,
+                     const uint64_t* anchor_round, const uint8_t* anchor_sig, size_t anchor_sig_len, size_t window, uint64_t seed,
+                     uint8_t* status_out, uint64_t counts_out[6]);
+void dh_archive_close(dh_archive* archive);
+
+/*
  * Live kernel timing: when enabled, every device stage of the verification path is bracketed by HIP
  * events on the stream it is launched on; dh_profile_read writes a JSON object
  * {"stage": {"count": c, "total_ms": t}, ...} into buf (returns the full length). dh_profile resets.
