@@ -35,6 +35,7 @@
 #include "bolt.hpp"
 #include "bolt_write.hpp"
 #include "kernels.hpp"
+#include "pbwire.hpp"
 #include "rdjson.hpp"
 
 namespace {
@@ -4336,9 +4337,14 @@ struct dh_archive {
   dbuf rounds, sigs, sig_lens, prevs, prev_lens, rands, rand_lens, defer, verdict, rand_out, status;
   dbuf carry, carry_round, carry_len, carry_sig;  // the record before the window
   std::vector<uint8_t> h_defer;
+  // protobuf handles (dh_archive_open_pb): the record kind, the expected beacon ID and the window's metadata bytes
+  int kind = 0;
+  bool has_id = false;
+  uint32_t id_len = 0;
+  dbuf d_id, meta;
   void release() {
     for (dbuf* b : {&d_file, &cnt, &base, &scan_tmp, &line_off, &line_len, &chunks, &d_stat, &rounds, &sigs, &sig_lens, &prevs, &prev_lens,
-                    &rands, &rand_lens, &defer, &verdict, &rand_out, &status, &carry, &carry_round, &carry_len, &carry_sig})
+                    &rands, &rand_lens, &defer, &verdict, &rand_out, &status, &carry, &carry_round, &carry_len, &carry_sig, &d_id, &meta})
       b->release();
     if (st) (void)hipStreamDestroy(st);
     st = nullptr;
@@ -4421,9 +4427,18 @@ static int archive_open(dh_archive* a, const uint8_t* buf, size_t len) {
 }
 
 // records [first, first + n) of the archive into the columns; waits for the stream
-static int archive_gather(dh_archive* a, uint64_t first, size_t n, const dh::archive_cols& c) {
+static int archive_gather(dh_archive* a, uint64_t first, size_t n, const dh::archive_cols& c, uint8_t* meta = nullptr) {
   if (!n) return DH_OK;
   timed_launches tl(a->st);  // resolved after the stream wait below
+  if (a->kind) {
+    const dh::pb_meta_out x{meta, a->d_id.as<uint8_t>(), a->id_len};
+    HIP_TRY(tl.run("k_pb_gather", [&] {
+      return dh::launch_pb_gather(a->kind, a->d_file.as<uint8_t>(), a->len, a->line_off.as<uint64_t>() + first,
+                                  a->line_len.as<uint32_t>() + first, n, c, x, a->st);
+    }));
+    HIP_TRY(hipStreamSynchronize(a->st));
+    return DH_OK;
+  }
   HIP_TRY(tl.run("k_ndjson_gather", [&] {
     return dh::launch_ndjson_gather(a->d_file.as<uint8_t>(), a->len, a->line_off.as<uint64_t>() + first, a->line_len.as<uint32_t>() + first, n,
                                     c, a->st);
@@ -4457,6 +4472,181 @@ int dh_archive_open_ndjson(const uint8_t* buf, size_t len, dh_archive** out) {
   std::lock_guard<std::mutex> lk(g_stores_mu);
   g_archives.push_back(a);
   *out = a;
+  return DH_OK;
+}
+
+int dh_archive_open_pb(int kind, const uint8_t* buf, size_t len, const uint64_t* rec_off, const uint32_t* rec_len, size_t n_rec, dh_archive** out) {
+  if (!out || (len && !buf) || (n_rec && !rec_len)) return fail(DH_EINVAL, "null argument");
+  *out = nullptr;
+  if (kind != DH_PB_BEACON_PACKET && kind != DH_PB_PUBLIC_RAND) return fail(DH_EINVAL, "unknown record kind %d", kind);
+  if (len > store_max_bytes())
+    return fail(DH_ENOMEM, "archive of %zu bytes exceeds DRANDHIP_STORE_MAX_BYTES (%zu): keep the host reader", len, store_max_bytes());
+  if (len >> 33) return fail(DH_ENOMEM, "archive of %zu bytes: at most 8 GiB per handle: split it between two records", len);
+  if (n_rec >> 32) return fail(DH_ENOMEM, "%zu records: the record index is 32 bits wide: split the buffer", n_rec);
+  // the offsets, summed or checked here in 64 bits: ascending, no overlap, every record inside the buffer
+  std::vector<uint64_t> off(n_rec + 1);
+  uint64_t at = 0;
+  for (size_t i = 0; i < n_rec; i++) {
+    const uint64_t o = rec_off ? rec_off[i] : at;
+    if (o < at || o > len || rec_len[i] > len - o)
+      return fail(DH_EINVAL, "record %zu ([%llu, +%u)) lies outside the buffer of %zu bytes or before the end of record %zu - 1", i,
+                  (unsigned long long)o, rec_len[i], len, i);
+    off[i] = o;
+    at = o + rec_len[i];
+  }
+  if (!rec_off && at != len) return fail(DH_EINVAL, "the %zu record lengths sum to %llu, the buffer holds %zu bytes", n_rec, (unsigned long long)at, len);
+  int rc = ensure_device();
+  if (rc) return rc;
+  dh_archive* a = new dh_archive();
+  a->kind = kind;
+  a->len = len;
+  a->nrec = n_rec;
+  a->stat[6] = 0;
+  auto open = [&]() -> int {
+    HIP_TRY(hipStreamCreateWithFlags(&a->st, hipStreamNonBlocking));
+    {
+      prof_wall p("archive_upload");
+      HIP_TRY(a->d_file.ensure(std::max<size_t>(len, 16)));
+      HIP_TRY(a->line_off.ensure(n_rec * 8 + 8));
+      HIP_TRY(a->line_len.ensure(n_rec * 4 + 4));
+      HIP_TRY(a->d_id.ensure(16));
+      if (len) HIP_TRY(hipMemcpyAsync(a->d_file.p, buf, len, hipMemcpyHostToDevice, a->st));
+      if (n_rec) {
+        HIP_TRY(hipMemcpyAsync(a->line_off.p, off.data(), n_rec * 8, hipMemcpyHostToDevice, a->st));
+        HIP_TRY(hipMemcpyAsync(a->line_len.p, rec_len, n_rec * 4, hipMemcpyHostToDevice, a->st));
+      }
+      HIP_TRY(hipStreamSynchronize(a->st));
+    }
+    prof_wall p("archive_stat");
+    uint64_t st5[5];
+    HIP_TRY(a->chunks.ensure((n_rec / 64 + 1) * sizeof(dh::archive_stat)));
+    HIP_TRY(a->d_stat.ensure(sizeof st5));
+    HIP_TRY(dh::launch_pb_stat(kind, a->d_file.as<uint8_t>(), len, a->line_off.as<uint64_t>(), a->line_len.as<uint32_t>(), n_rec, a->chunks.p,
+                               a->d_stat.as<uint64_t>(), a->st));
+    HIP_TRY(hipMemcpyAsync(st5, a->d_stat.p, sizeof st5, hipMemcpyDeviceToHost, a->st));
+    HIP_TRY(hipStreamSynchronize(a->st));
+    a->stat[0] = n_rec;
+    memcpy(a->stat + 1, st5, sizeof st5);
+    return DH_OK;
+  };
+  if ((rc = open())) {
+    a->release();
+    delete a;
+    return rc;
+  }
+  std::lock_guard<std::mutex> lk(g_stores_mu);
+  g_archives.push_back(a);
+  *out = a;
+  return DH_OK;
+}
+
+int dh_archive_kind(const dh_archive* a) { return a ? a->kind : fail(DH_EINVAL, "null argument"); }
+
+int dh_archive_set_beacon_id(dh_archive* a, const uint8_t* id, size_t id_len) {
+  if (!a) return fail(DH_EINVAL, "null argument");
+  if (id_len > dh::bolt::PBWIRE_MAX_RECORD) return fail(DH_EINVAL, "beacon ID of %zu bytes: no record of 4096 bytes holds it", id_len);
+  archive_guard g(a);
+  int rc = archive_enter(a);
+  if (rc) return rc;
+  a->has_id = id != nullptr;
+  a->id_len = id ? (uint32_t)id_len : 0;
+  if (a->id_len) {
+    HIP_TRY(a->d_id.ensure(a->id_len));
+    HIP_TRY(hipMemcpy(a->d_id.p, id, a->id_len, hipMemcpyHostToDevice));
+  }
+  return DH_OK;
+}
+
+int dh_pb_frame_delimited(const uint8_t* buf, size_t len, uint64_t* off_out, uint32_t* len_out, size_t cap, size_t* n_out,
+                          size_t* consumed_out) {
+  if (!n_out || !consumed_out || (len && !buf) || (cap && (!off_out || !len_out))) return fail(DH_EINVAL, "null argument");
+  uint64_t consumed = 0;
+  const uint64_t n = dh::bolt::pb_frame_delimited(dh::bolt::view{buf, (uint64_t)len}, off_out, len_out, cap, &consumed);
+  *n_out = (size_t)n;
+  if (n > cap) {
+    *consumed_out = 0;
+    return fail(DH_EINVAL, "%llu records, room for %zu", (unsigned long long)n, cap);
+  }
+  *consumed_out = (size_t)consumed;
+  return DH_OK;
+}
+
+int dh_pb_encode_device(int kind, const uint64_t* d_rounds, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_lens,
+                        const uint8_t* d_prevs, size_t prev_stride, const uint32_t* d_prev_lens, size_t n, const uint8_t* beacon_id,
+                        size_t beacon_id_len, int delimited, uint8_t* d_out, size_t cap, uint32_t* d_rec_len_out, size_t* len_out,
+                        void* hip_stream) {
+  if (!len_out) return fail(DH_EINVAL, "null argument");
+  *len_out = 0;
+  if (kind != DH_PB_BEACON_PACKET)
+    return fail(DH_EINVAL, "record kind %d: only BeaconPacket (%d) is encoded (PublicRandResponse needs the randomness digest)", kind,
+                DH_PB_BEACON_PACKET);
+  if (!d_prevs != !d_prev_lens) return fail(DH_EINVAL, "d_prevs and d_prev_lens are given together or not at all");
+  if (n > ARCHIVE_CALL_ROWS) return fail(DH_EINVAL, "%zu rows: at most 16M rows per call: split the call", n);
+  if (n && (!d_rounds || !d_sigs || !d_sig_lens)) return fail(DH_EINVAL, "null column");
+  if (!sig_stride || (sig_stride & 3) || sig_stride > ((size_t)1 << 20) || ((uintptr_t)d_sigs & 3) ||
+      (d_prevs && (!prev_stride || (prev_stride & 3) || prev_stride > ((size_t)1 << 20) || ((uintptr_t)d_prevs & 3))))
+    return fail(DH_EINVAL, "rows are 4-byte aligned with strides %zu / %zu that are positive multiples of 4, at most 1 MiB", sig_stride, prev_stride);
+  // the metadata field, the same for every row: 22 M [12 L id]
+  std::vector<uint8_t> meta;
+  auto varint = [&](uint64_t v) {
+    for (; v >> 7; v >>= 7) meta.push_back((uint8_t)(v | 0x80));
+    meta.push_back((uint8_t)v);
+  };
+  if (beacon_id) {
+    if (beacon_id_len > dh::bolt::PBWIRE_MAX_RECORD) return fail(DH_EINVAL, "beacon ID of %zu bytes: a record holds at most 4096", beacon_id_len);
+    std::vector<uint8_t> inner;
+    std::swap(inner, meta);
+    if (beacon_id_len) {
+      meta.push_back(0x12);
+      varint(beacon_id_len);
+      meta.insert(meta.end(), beacon_id, beacon_id + beacon_id_len);
+    }
+    std::swap(inner, meta);
+    meta.push_back(0x22);
+    varint(inner.size());
+    meta.insert(meta.end(), inner.begin(), inner.end());
+  }
+  int rc = ensure_device();
+  if (rc) return rc;
+  if (!n) return DH_OK;
+  HIP_TRY(hipSetDevice(g_ctx.device));
+  prof_wall p("packet_encode");
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(hipStreamSynchronize(st));  // the columns may be written there
+  const size_t nsum = (n + 255) / 256;
+  dbuf d_meta, frame, off, scan_tmp, sums;
+  struct free_all {
+    dbuf* b[5];
+    ~free_all() {
+      for (dbuf* x : b) x->release();
+    }
+  } guard{{&d_meta, &frame, &off, &scan_tmp, &sums}};
+  HIP_TRY(d_meta.ensure(std::max<size_t>(meta.size(), 4)));
+  HIP_TRY(frame.ensure(n * 4));
+  HIP_TRY(off.ensure((n + 1) * 4));
+  HIP_TRY(scan_tmp.ensure((n / 4096 + 2) * 4));
+  HIP_TRY(sums.ensure(nsum * sizeof(dh::pb_size_sum)));
+  if (!meta.empty()) HIP_TRY(hipMemcpyAsync(d_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, st));
+  const dh::pb_encode_in e{d_rounds, d_sigs, d_sig_lens, d_prevs, d_prev_lens, d_meta.as<uint8_t>(), (uint32_t)sig_stride,
+                           (uint32_t)(d_prevs ? prev_stride : 4), (uint32_t)meta.size(), delimited ? 1u : 0u};
+  timed_launches tl(st);
+  HIP_TRY(tl.run("k_pb_size", [&] { return dh::launch_pb_size(e, n, d_rec_len_out, frame.as<uint32_t>(), sums.as<dh::pb_size_sum>(), st); }));
+  std::vector<dh::pb_size_sum> h_sums(nsum);
+  HIP_TRY(hipMemcpyAsync(h_sums.data(), sums.p, nsum * sizeof(dh::pb_size_sum), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint64_t total = 0;
+  for (const dh::pb_size_sum& x : h_sums) {
+    if (x.first_bad != ~0ull)
+      return fail(DH_EINVAL, "row %llu: its packet would exceed 4096 bytes, or a length passes its row's stride", (unsigned long long)x.first_bad);
+    total += x.bytes;
+  }
+  if (total >> 32) return fail(DH_EINVAL, "%llu bytes of packets: 4 GiB or more in one call: split the call", (unsigned long long)total);
+  *len_out = (size_t)total;
+  if (!d_out) return DH_OK;
+  if (cap < total) return fail(DH_EINVAL, "%llu bytes of packets, room for %zu", (unsigned long long)total, cap);
+  HIP_TRY(dh::launch_scan(frame.as<uint32_t>(), n, off.as<uint32_t>(), scan_tmp.as<uint32_t>(), st));
+  HIP_TRY(tl.run("k_pb_encode", [&] { return dh::launch_pb_encode(e, n, off.as<uint32_t>(), d_out, st); }));
+  HIP_TRY(hipStreamSynchronize(st));
   return DH_OK;
 }
 
@@ -4586,6 +4776,11 @@ int dh_archive_check(dh_archive* a, int scheme, const uint8_t* pk, size_t pk_len
   HIP_TRY(a->verdict.ensure(wmax));
   HIP_TRY(a->rand_out.ensure(wmax * 32));
   HIP_TRY(a->status.ensure(wmax));
+  uint8_t* meta = nullptr;  // the beacon-ID check of tryNode: protobuf handles with an expected ID only
+  if (a->kind && a->has_id) {
+    HIP_TRY(a->meta.ensure(wmax));
+    meta = a->meta.as<uint8_t>();
+  }
   const dh::archive_cols c{a->rounds.as<uint64_t>(), a->defer.as<uint8_t>(), a->sigs.as<uint8_t>(), a->sig_lens.as<uint32_t>(),
                            chained ? a->prevs.as<uint8_t>() : nullptr, chained ? a->prev_lens.as<uint32_t>() : nullptr,
                            a->rands.as<uint8_t>(), a->rand_lens.as<uint32_t>(), (uint32_t)stride, (uint32_t)stride};
@@ -4614,7 +4809,7 @@ int dh_archive_check(dh_archive* a, int scheme, const uint8_t* pk, size_t pk_len
     const size_t m = std::min(window, n_rec - at);
     {
       prof_wall p("archive_gather");
-      if ((rc = archive_gather(a, first_rec + at, m, c))) return rc;
+      if ((rc = archive_gather(a, first_rec + at, m, c, meta))) return rc;
     }
     {
       prof_wall p("archive_verify");
@@ -4628,7 +4823,7 @@ int dh_archive_check(dh_archive* a, int scheme, const uint8_t* pk, size_t pk_len
     prof_wall p("archive_fold");
     const dh::archive_fold_in f{m, sig_len, chained ? 1u : 0u, (uint32_t)stride, (uint32_t)stride, a->verdict.as<uint8_t>(),
                                 a->rand_out.as<uint8_t>(), c.rounds, c.deferred, c.sigs, c.sig_lens, c.prevs, c.prev_lens, c.rands, c.rand_lens,
-                                a->carry.as<uint8_t>(), a->carry_round.as<uint64_t>(), a->carry_len.as<uint32_t>(), a->carry_sig.as<uint8_t>()};
+                                a->carry.as<uint8_t>(), a->carry_round.as<uint64_t>(), a->carry_len.as<uint32_t>(), a->carry_sig.as<uint8_t>(), meta};
     HIP_TRY(dh::launch_archive_fold(f, a->status.as<uint8_t>(), a->st));
     HIP_TRY(hipMemcpyAsync(status_out + at, a->status.p, m, hipMemcpyDeviceToHost, a->st));
     if ((rc = carry_row(m - 1))) return rc;

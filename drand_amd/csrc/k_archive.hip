@@ -5,10 +5,11 @@
 //   k_ndjson_stat    one wave per chunk of 64 records: deferred records, longest line and decoded fields; then
 //   k_ndjson_stat_fold folds the chunks
 //   k_ndjson_gather  one wave per chunk of 64 records of a window: the columns dh_verify_batch_device takes
-//   k_archive_fold   per record: the status byte of dh_archive_check
+//   k_archive_fold   per record: the status byte of dh_archive_check (also behind k_packet.hip's protobuf gather)
 // Memory-bound and small next to verification; plain C++, vector stores, no atomics anywhere.
 #include <hip/hip_runtime.h>
 
+#include "archive_chunk.hpp"
 #include "kernels.hpp"
 #include "rdjson.hpp"
 #include "sha256.hpp"
@@ -18,9 +19,7 @@ using namespace bolt;
 
 namespace {
 constexpr uint32_t TILE = ARCHIVE_TILE, ROW = 256;  // a wave reads a tile in rows of 64 dwords
-constexpr uint32_t LDS_CHUNK = 36864;               // a chunk of up to 36 KiB is staged in LDS; larger ones are read in place
 constexpr uint32_t MAX_LEN = RDJSON_MAX_LINE + 1;   // the length recorded for every longer line
-inline unsigned nblk(size_t n, unsigned t) { return (unsigned)((n + t - 1) / t); }
 
 // the dword at pos (a multiple of 4); bytes at or beyond len read as '\n'
 __device__ __forceinline__ uint32_t tile_word(const uint8_t* __restrict__ file, uint64_t len, uint64_t pos) {
@@ -105,33 +104,6 @@ __global__ __launch_bounds__(64) void k_ndjson_index(const uint8_t* __restrict__
 }
 
 namespace {
-// The bytes of records [0, cnt) of a chunk (cnt <= 64, consecutive in the file) behind one pointer: staged in LDS
-// with 16-byte loads when they fit, else the file itself. *origin = the file offset of the returned pointer.
-__device__ __forceinline__ const uint8_t* stage_chunk(const uint8_t* __restrict__ file, uint64_t len, const uint64_t* __restrict__ line_off,
-                                                      const uint32_t* __restrict__ line_len, uint32_t cnt, uint4* lds, uint64_t* origin) {
-  const uint64_t a = line_off[0] & ~15ull, b = line_off[cnt - 1] + line_len[cnt - 1];  // b <= len: the index measured it
-  if (b - a > LDS_CHUNK) {
-    *origin = 0;
-    return file;
-  }
-  const uint32_t nq = (uint32_t)((b - a + 15) / 16);
-  for (uint32_t i = threadIdx.x; i < nq; i += 64) {
-    const uint64_t p = a + 16 * (uint64_t)i;
-    uint4 q;
-    if (p + 16 <= len) {
-      q = *(const uint4*)(file + p);
-    } else {  // the image's last bytes
-      uint32_t w[4] = {0, 0, 0, 0};
-      for (uint32_t k = 0; k < 16 && p + k < len; k++) w[k / 4] |= (uint32_t)file[p + k] << (8 * (k & 3));
-      q = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    lds[i] = q;
-  }
-  __syncthreads();
-  *origin = a;
-  return (const uint8_t*)lds;
-}
-
 // the chunk's rows are consecutive in the output: lane t writes dword t of them, decoded from 8 hex characters
 __device__ __forceinline__ void write_hex_rows(const uint8_t* src, uint8_t* __restrict__ rows, uint32_t stride, uint64_t row0, uint32_t cnt,
                                                const uint64_t* sel_off, const uint32_t* sel_hex) {
@@ -305,6 +277,7 @@ __global__ __launch_bounds__(256) void k_archive_fold(const archive_fold_in f, u
         st |= AR_LINK;
     }
   }
+  if (f.meta && (f.meta[i] & 3) == 1) st |= AR_BEACON_ID;  // metadata with another beaconID (sync_manager.go:385-389)
   status[i] = (uint8_t)st;
 }
 
@@ -320,7 +293,10 @@ hipError_t launch_ndjson_index(const uint8_t* file, uint64_t len, size_t ntiles,
 hipError_t launch_ndjson_stat(const uint8_t* file, uint64_t len, const uint64_t* line_off, const uint32_t* line_len, size_t n, void* chunks,
                               uint64_t* out5, hipStream_t st) {
   if (n) hipLaunchKernelGGL(k_ndjson_stat, dim3(nblk(n, 64)), dim3(64), 0, st, file, len, line_off, line_len, (uint64_t)n, (archive_stat*)chunks);
-  hipLaunchKernelGGL(k_ndjson_stat_fold, dim3(1), dim3(256), 0, st, (const archive_stat*)chunks, (size_t)nblk(n, 64), out5);
+  return launch_ndjson_stat_fold(chunks, nblk(n, 64), out5, st);
+}
+hipError_t launch_ndjson_stat_fold(const void* chunks, size_t n_chunks, uint64_t* out5, hipStream_t st) {
+  hipLaunchKernelGGL(k_ndjson_stat_fold, dim3(1), dim3(256), 0, st, (const archive_stat*)chunks, n_chunks, out5);
   return hipGetLastError();
 }
 hipError_t launch_ndjson_gather(const uint8_t* file, uint64_t len, const uint64_t* line_off, const uint32_t* line_len, size_t n,

@@ -339,7 +339,7 @@ struct archive_cols {
   uint32_t* rand_lens;
   uint32_t sig_stride, prev_stride;
 };
-enum : uint32_t { AR_DEFERRED = 1, AR_NO_SIGNATURE = 2, AR_INVALID = 4, AR_RANDOMNESS = 8, AR_SEQUENCE = 16, AR_LINK = 32, AR_PRED_DEFERRED = 64 };
+enum : uint32_t { AR_DEFERRED = 1, AR_NO_SIGNATURE = 2, AR_INVALID = 4, AR_RANDOMNESS = 8, AR_SEQUENCE = 16, AR_LINK = 32, AR_PRED_DEFERRED = 64, AR_BEACON_ID = 128 };
 struct archive_fold_in {
   size_t n;
   uint32_t want_sig_len, chained, sig_stride, prev_stride;
@@ -358,6 +358,8 @@ struct archive_fold_in {
   const uint64_t* carry_round;
   const uint32_t* carry_len;
   const uint8_t* carry_sig;
+  // protobuf handles with an expected beacon ID (else NULL): pb_meta_out's byte per row; AR_BEACON_ID = bit 0 without bit 1
+  const uint8_t* meta;
 };
 hipError_t launch_ndjson_count(const uint8_t* file, uint64_t len, size_t ntiles, uint32_t* cnt, hipStream_t st);
 hipError_t launch_ndjson_index(const uint8_t* file, uint64_t len, size_t ntiles, const uint32_t* base, uint64_t* line_off, uint32_t* line_len,
@@ -367,6 +369,39 @@ hipError_t launch_ndjson_stat(const uint8_t* file, uint64_t len, const uint64_t*
 hipError_t launch_ndjson_gather(const uint8_t* file, uint64_t len, const uint64_t* line_off, const uint32_t* line_len, size_t n,
                                 const archive_cols& c, hipStream_t st);
 hipError_t launch_archive_fold(const archive_fold_in& f, uint8_t* status, hipStream_t st);
+hipError_t launch_ndjson_stat_fold(const void* chunks, size_t n_chunks, uint64_t* out5, hipStream_t st);
+
+// protobuf beacon records (k_packet.hip, pbwire.hpp). kind: 1 BeaconPacket, 2 PublicRandResponse. The
+// caller gives rec_off / rec_len (ascending, inside the image); stat and gather are launch_ndjson_stat / _gather for
+// these records, with the same columns and rules. pb_meta_out (meta nullable): per record bit 0 = metadata present,
+// bit 1 = its beaconID equals want[0, want_len). The encoder: size gives each row's BeaconPacket length (rec_len,
+// nullable; 0 for a row that cannot be encoded), its frame length (with the varint prefix when delimited) and one
+// pb_size_sum per 256 rows; then launch_scan over frame_len (off, n + 1 words) and encode. sigs / prevs rows are
+// 4-byte aligned with strides that are multiples of 4; prevs / prev_lens NULL together; meta = the metadata field's
+// bytes (tag 0x22 included), meta_len 0 for none.
+struct pb_meta_out {
+  uint8_t* meta;
+  const uint8_t* want;
+  uint32_t want_len;
+};
+struct pb_encode_in {
+  const uint64_t* rounds;
+  const uint8_t* sigs;
+  const uint32_t* sig_lens;
+  const uint8_t* prevs;
+  const uint32_t* prev_lens;
+  const uint8_t* meta;
+  uint32_t sig_stride, prev_stride, meta_len, delimited;
+};
+struct pb_size_sum {
+  uint64_t bytes, first_bad;  // first_bad: the first row that cannot be encoded, ~0 for none
+};
+hipError_t launch_pb_stat(int kind, const uint8_t* file, uint64_t len, const uint64_t* rec_off, const uint32_t* rec_len, size_t n, void* chunks,
+                          uint64_t* out5, hipStream_t st);
+hipError_t launch_pb_gather(int kind, const uint8_t* file, uint64_t len, const uint64_t* rec_off, const uint32_t* rec_len, size_t n,
+                            const archive_cols& c, const pb_meta_out& x, hipStream_t st);
+hipError_t launch_pb_size(const pb_encode_in& e, size_t n, uint32_t* rec_len, uint32_t* frame_len, pb_size_sum* sums, hipStream_t st);
+hipError_t launch_pb_encode(const pb_encode_in& e, size_t n, const uint32_t* off, uint8_t* out, hipStream_t st);
 
 // verifier columns -> the leaf pages of a trimmed bbolt store (k_bolt_write.hip). need: the record
 // sizes 24 + lens[i] (then launch_scan), err_word set when rounds do not ascend or a length passes the stride. pack:

@@ -903,6 +903,8 @@ _U64 = (1 << 64) - 1
 AR_DEFERRED, AR_NO_SIGNATURE, AR_INVALID, AR_RANDOMNESS = (_lib.DH_AR_DEFERRED, _lib.DH_AR_NO_SIGNATURE, _lib.DH_AR_INVALID,
                                                           _lib.DH_AR_RANDOMNESS)
 AR_SEQUENCE, AR_LINK, AR_PRED_DEFERRED = _lib.DH_AR_SEQUENCE, _lib.DH_AR_LINK, _lib.DH_AR_PRED_DEFERRED
+AR_BEACON_ID = _lib.DH_AR_BEACON_ID
+PB_BEACON_PACKET, PB_PUBLIC_RAND = _lib.DH_PB_BEACON_PACKET, _lib.DH_PB_PUBLIC_RAND
 _RD_FIELDS = ("randomness", "signature", "previous_signature")
 
 
@@ -1020,25 +1022,77 @@ class DeviceArchive:
     """A client.RandomData JSON-lines archive parsed on the device (dh_archive_*): the image is uploaded
     and indexed once; beacons_device gives a window's columns as torch tensors in the layout dh_verify_batch_device and
     BoltWriter.append take; check verifies every record and resolves the records the device defers here, through
-    random_data_from_line. A context manager. The JSON-array form raises ValueError: read_random_data reads it."""
+    random_data_from_line. A context manager. The JSON-array form raises ValueError: read_random_data reads it.
+    from_packets opens the same handle over protobuf records."""
 
     STAT = ("records", "deferred", "longest_line", "longest_signature", "longest_previous", "longest_randomness", "tile_bytes")
 
+    kind = 0       # 0: JSON lines; PB_BEACON_PACKET / PB_PUBLIC_RAND: protobuf records (from_packets)
+    unframed = b""  # from_packets on a varint-delimited buffer: the trailing bytes that frame no record
+
     def __init__(self, path_or_bytes):
-        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
-            self._data = bytes(path_or_bytes)
-        else:
-            with open(path_or_bytes, "rb") as f:
-                self._data = f.read()
+        self._data = self._read(path_or_bytes)
         self._h = None
         self._resolved = {}
-        lib = _lib.load()
         h = ctypes.c_void_p()
-        DeviceBoltStore._raise(lib.dh_archive_open_ndjson(self._data, len(self._data), ctypes.byref(h)))
+        DeviceBoltStore._raise(_lib.load().dh_archive_open_ndjson(self._data, len(self._data), ctypes.byref(h)))
+        self._opened(h)
+
+    @staticmethod
+    def _read(path_or_bytes):
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            return bytes(path_or_bytes)
+        with open(path_or_bytes, "rb") as f:
+            return f.read()
+
+    def _opened(self, h):
         self._h = h
         st = (ctypes.c_uint64 * 7)()
-        DeviceBoltStore._raise(lib.dh_archive_stat(h, st))
+        DeviceBoltStore._raise(_lib.load().dh_archive_stat(h, st))
         self._stat = [int(x) for x in st]
+
+    @classmethod
+    def from_packets(cls, kind, data, lens=None, offs=None):
+        """Protobuf records of `kind` (PB_BEACON_PACKET: SyncChain's BeaconPacket, PB_PUBLIC_RAND: the
+        relays' PublicRandResponse). data: bytes, a path, or a list of byte strings (joined here, one record each). lens
+        (and optionally offs, the records' offsets; else they are packed from 0) frame the records of a buffer: a gossip
+        subscriber or a raw gRPC codec holds them. With neither, the buffer is varint-delimited and framed on the host by
+        dh_pb_frame_delimited (a convenience for files, off the hot path); the trailing bytes that frame no record are
+        .unframed. Everything else is DeviceArchive's: deferred records go through packet_from_bytes."""
+        lib = _lib.load()
+        self = cls.__new__(cls)
+        self._h = None
+        self._resolved = {}
+        self.kind = int(kind)
+        if isinstance(data, (list, tuple)):
+            if lens is not None or offs is not None:
+                raise ValueError("a list of records frames itself")
+            lens = np.array([len(b) for b in data], np.uint32)
+            data = b"".join(bytes(b) for b in data)
+        self._data = self._read(data)
+        n_all = len(self._data)
+        if lens is None:
+            if offs is not None:
+                raise ValueError("offs without lens")
+            n, used = ctypes.c_size_t(0), ctypes.c_size_t(0)
+            offs, lens = np.zeros(0, np.uint64), np.zeros(0, np.uint32)
+            rc = lib.dh_pb_frame_delimited(self._data, n_all, None, None, 0, ctypes.byref(n), ctypes.byref(used))
+            if n.value:  # DH_EINVAL with the count
+                offs, lens = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint32)
+                rc = lib.dh_pb_frame_delimited(self._data, n_all, ctypes.c_void_p(offs.ctypes.data), ctypes.c_void_p(lens.ctypes.data),
+                                               n.value, ctypes.byref(n), ctypes.byref(used))
+            DeviceBoltStore._raise(rc)
+            self.unframed = self._data[used.value:]
+        lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        if offs is not None:
+            offs = np.ascontiguousarray(offs, dtype=np.uint64)
+            if len(offs) != len(lens):
+                raise ValueError("%d offsets, %d lengths" % (len(offs), len(lens)))
+        h = ctypes.c_void_p()
+        DeviceBoltStore._raise(lib.dh_archive_open_pb(self.kind, self._data, n_all, ctypes.c_void_p(offs.ctypes.data) if offs is not None and len(offs) else None,
+                                                      ctypes.c_void_p(lens.ctypes.data) if len(lens) else None, len(lens), ctypes.byref(h)))
+        self._opened(h)
+        return self
 
     def close(self):
         if self._h is not None:
@@ -1070,7 +1124,7 @@ class DeviceArchive:
 
     def lines(self, first=0, n=None):
         """(byte offsets uint64[n], lengths uint32[n]) of records first .. first + n - 1; a line above 4096 bytes has
-        length 4097."""
+        length 4097 (a protobuf record: its payload's offset and true length, as the caller gave them)."""
         first, n = self._window(first, n)
         off, ln = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
         DeviceBoltStore._raise(_lib.load().dh_archive_lines(self._h, first, n, ctypes.c_void_p(off.ctypes.data),
@@ -1079,9 +1133,11 @@ class DeviceArchive:
 
     def line(self, i):
         """The bytes of record i, from the host copy (whatever its length)."""
-        off, _ = self.lines(i, 1)
+        off, ln = self.lines(i, 1)
         if not len(off):
             raise IndexError(i)
+        if self.kind:
+            return self._data[int(off[0]):int(off[0]) + int(ln[0])]
         end = self._data.find(b"\n", int(off[0]))
         return self._data[int(off[0]):end if end >= 0 else len(self._data)]
 
@@ -1124,6 +1180,11 @@ class DeviceArchive:
             ptr(rand_lens), ptr(deferred), ctypes.byref(k), None))
         return rounds, sigs, sig_lens, prevs, prev_lens, rands, rand_lens, deferred
 
+    def set_beacon_id(self, beacon_id):
+        """The ID check() compares every record's metadata with (protobuf handles; None: no comparison)."""
+        bid = _id_bytes(beacon_id)
+        DeviceBoltStore._raise(_lib.load().dh_archive_set_beacon_id(self._h, bid, len(bid or b"")))
+
     def check_device(self, scheme, pubkey, anchor=None, window=1 << 20, seed=0):
         """dh_archive_check over the whole archive: (status uint8[records] with the deferred records marked
         DH_AR_DEFERRED and undecided, counts dict)."""
@@ -1144,17 +1205,23 @@ class DeviceArchive:
         """Record i through the host decoder: a dict, None (whitespace only) or False (it does not decode); cached."""
         if i not in self._resolved:
             try:
-                self._resolved[i] = random_data_from_line(self.line(i))
+                self._resolved[i] = packet_from_bytes(self.kind, self.line(i)) if self.kind else random_data_from_line(self.line(i))
             except DECODE_ERRORS:
                 self._resolved[i] = False
         return self._resolved[i]
 
-    def check(self, scheme, pubkey, anchor=None, window=1 << 20, seed=0):
+    def check(self, scheme, pubkey, anchor=None, window=1 << 20, seed=0, beacon_id=None):
         """One status byte per record (numpy uint8; the DH_AR_* bits), equal to check_random_data_host over the same
         bytes. The device decides the canonical records; each deferred line is decided HERE, by random_data_from_line (this
         module's restatement, not a decoder pinned to nikkolasg/hexjson): a whitespace-only line is dropped from the
         result, one that does not decode gets DH_AR_INVALID, a decoded one is verified in one small verify_beacons call,
-        and the predecessor bits are computed for it and for the record after it."""
+        and the predecessor bits are computed for it and for the record after it. A protobuf handle decides its deferred
+        records with packet_from_bytes, equals check_packets_host, and compares each record's metadata with beacon_id
+        (DH_AR_BEACON_ID; None: no comparison)."""
+        if self.kind:
+            self.set_beacon_id(beacon_id)
+        elif beacon_id is not None:
+            raise ValueError("a RandomData record carries no beacon ID")
         status, _ = self.check_device(scheme, pubkey, anchor, window, seed)
         todo = [int(i) for i in np.flatnonzero(status & (AR_DEFERRED | AR_PRED_DEFERRED))]
         if not todo:
@@ -1173,7 +1240,8 @@ class DeviceArchive:
         for i in todo:
             if status[i] & AR_DEFERRED:
                 r = dec[i]
-                out[i] = AR_INVALID if not r else _own_bits(r, scheme.sig_len, verdict.get(id(r), False)) | _pred_bits(r, pred_of(i), scheme.chained)
+                out[i] = AR_INVALID if not r else (_own_bits(r, scheme.sig_len, verdict.get(id(r), False)) |
+                                                   _pred_bits(r, pred_of(i), scheme.chained) | _id_bits(r, beacon_id))
             else:  # canonical, behind a deferred record
                 out[i] = (int(status[i]) & ~AR_PRED_DEFERRED) | _pred_bits(self.resolve(i), pred_of(i), scheme.chained)
         keep = np.ones(len(out), bool)
@@ -1223,3 +1291,299 @@ def archive_to_trimmed_store(archive, path, scheme, pubkey, anchor=None, window=
     finally:
         if own:
             ar.close()
+
+
+# ---- protobuf beacon records: BeaconPacket (protobuf/drand/protocol.proto:113-118 of the reference)
+# and PublicRandResponse (protobuf/drand/api.proto:44-52), with common.Metadata / common.NodeVersion inside
+
+_PB_NODE_VERSION = {1: ("u32", "major"), 2: ("u32", "minor"), 3: ("u32", "patch"), 4: ("str", "prerelease")}
+_PB_METADATA = {1: ("msg", "node_version", _PB_NODE_VERSION), 2: ("str", "beacon_id"), 3: ("bytes", "chain_hash")}
+_PB_SCHEMA = {
+    PB_BEACON_PACKET: {1: ("bytes", "previous_signature"), 2: ("u64", "round"), 3: ("bytes", "signature"), 4: ("msg", "metadata", _PB_METADATA)},
+    PB_PUBLIC_RAND: {1: ("u64", "round"), 2: ("bytes", "signature"), 3: ("bytes", "previous_signature"), 4: ("bytes", "randomness"),
+                     5: ("msg", "metadata", _PB_METADATA)},
+}
+_PB_WIRE = {"u32": 0, "u64": 0, "str": 2, "bytes": 2, "msg": 2}
+
+
+def _id_bytes(beacon_id):
+    if beacon_id is None:
+        return None
+    return beacon_id.encode("utf-8") if isinstance(beacon_id, str) else bytes(beacon_id)
+
+
+def _id_bits(rec, beacon_id):
+    """DH_AR_BEACON_ID of a decoded record: metadata present and its beaconID is not the expected one (tryNode,
+    chain/beacon/sync_manager.go:385-389); nothing without an expected ID."""
+    if beacon_id is None or rec.get("beacon_id") is None:
+        return 0
+    return AR_BEACON_ID if _id_bytes(rec["beacon_id"]) != _id_bytes(beacon_id) else 0
+
+
+def _pb_put_varint(out, v):
+    while v >> 7:
+        out.append((v & 0x7F) | 0x80)
+        v >>= 7
+    out.append(v)
+
+
+def _pb_put(out, schema, rec):
+    """proto.Marshal of a proto3 message: field-number order, zero / empty scalars left out, a sub-message written when
+    it is present (not None), a string with explicit presence ("prerelease") likewise."""
+    for num in sorted(schema):
+        typ, name = schema[num][:2]
+        v = rec.get(name)
+        if typ == "msg":
+            if v is None:
+                continue
+            body = bytearray()
+            _pb_put(body, schema[num][2], v)
+        elif typ in ("u32", "u64"):
+            v = int(v or 0)
+            if not 0 <= v < (1 << (32 if typ == "u32" else 64)):
+                raise ValueError("%s = %d does not fit" % (name, v))
+            if v:
+                out.append(num << 3)
+                _pb_put_varint(out, v)
+            continue
+        else:
+            if name == "prerelease":
+                if v is None:
+                    continue
+            elif not v:
+                continue
+            body = v.encode("utf-8") if isinstance(v, str) else bytes(v)
+        out.append((num << 3) | 2)
+        _pb_put_varint(out, len(body))
+        out += body
+
+
+def packet_bytes(kind, rec, beacon_id=None):
+    """The wire form proto.Marshal writes for one record of `kind` (PB_BEACON_PACKET: beaconToProto,
+    chain/beacon/convert.go:9-16; PB_PUBLIC_RAND). rec: {round, signature, previous_signature[, randomness][, metadata]};
+    metadata: None (absent) or {beacon_id, chain_hash, node_version: None | {major, minor, patch, prerelease: None | str}}.
+    beacon_id (str or bytes; "" writes the empty sub-message) is the short form of metadata = {"beacon_id": beacon_id}."""
+    rec = dict(rec)
+    if beacon_id is not None:
+        rec["metadata"] = {"beacon_id": beacon_id}
+    out = bytearray()
+    _pb_put(out, _PB_SCHEMA[int(kind)], rec)
+    return bytes(out)
+
+
+def _pb_varint(b, i, most=10):
+    """A varint of up to `most` bytes, minimal or not, cut to 64 bits: (value, the index after it)."""
+    v = 0
+    for k in range(most):
+        if i + k >= len(b):
+            raise ValueError("varint cut short")
+        c = b[i + k]
+        v |= (c & 0x7F) << (7 * k)
+        if not c & 0x80:
+            return v & _U64, i + k + 1
+    raise ValueError("varint of more than %d bytes" % most)
+
+
+def _pb_tag(b, i, in_group=False):
+    tag, i = _pb_varint(b, i, 5)
+    if tag >> 32 or not (tag >> 3 or in_group):  # upb lets number 0 pass inside a group it skips; Go does not (DESIGN.md §26)
+        raise ValueError("field number %d" % (tag >> 3))
+    return tag >> 3, tag & 7, i
+
+
+def _pb_skip(b, i, num, wt, depth=0):
+    """The index after an unknown field's value (its tag already read); groups are walked to their end tag."""
+    if wt == 0:
+        return _pb_varint(b, i)[1]
+    if wt == 1 or wt == 5:
+        n = 8 if wt == 1 else 4
+        if len(b) - i < n:
+            raise ValueError("fixed value cut short")
+        return i + n
+    if wt == 2:
+        n, i = _pb_len(b, i)
+        return i + n
+    if wt == 3:
+        if depth >= 100:
+            raise ValueError("groups nested too deep")
+        while True:
+            if i >= len(b):
+                raise ValueError("group without end")
+            n2, w2, i = _pb_tag(b, i, True)
+            if w2 == 4:
+                if n2 != num:
+                    raise ValueError("end of another group")
+                return i
+            i = _pb_skip(b, i, n2, w2, depth + 1)
+    raise ValueError("wire type %d" % wt)
+
+
+def _pb_len(b, i):
+    n, i = _pb_varint(b, i)
+    if n >= (1 << 31) - 1 or n > len(b) - i:
+        raise ValueError("length %d runs past the end" % n)
+    return n, i
+
+
+def _pb_merge(schema, b, into, depth=0):
+    """Protobuf decoding of one message into `into`: last value wins, a repeated sub-message merges, unknown fields (and
+    known numbers with another wire type) are skipped, strings are UTF-8."""
+    if depth >= 100:
+        raise ValueError("messages nested too deep")
+    i = 0
+    while i < len(b):
+        num, wt, i = _pb_tag(b, i)
+        f = schema.get(num)
+        if f is None or _PB_WIRE[f[0]] != wt:
+            i = _pb_skip(b, i, num, wt)
+            continue
+        typ, name = f[:2]
+        if wt == 0:
+            v, i = _pb_varint(b, i)
+            into[name] = v & 0xFFFFFFFF if typ == "u32" else v
+            continue
+        n, i = _pb_len(b, i)
+        body = bytes(b[i:i + n])
+        i += n
+        if typ == "msg":
+            sub = into.get(name)
+            if sub is None:
+                sub = into[name] = {}
+            _pb_merge(f[2], body, sub, depth + 1)
+        else:
+            into[name] = body.decode("utf-8") if typ == "str" else body
+    return into
+
+
+def packet_from_bytes(kind, b):
+    """ONE protobuf record of `kind` -> {round, signature, previous_signature, randomness, metadata, beacon_id}: metadata
+    None when absent, else {beacon_id, chain_hash, node_version} as far as they were sent; beacon_id = metadata's
+    beaconID ("" when not sent), None without metadata. Raises ValueError for bytes that do not decode. This is the
+    project's restatement of protobuf decoding for these two messages, not the Go decoder: it decides the records the
+    device defers. Last value wins, a repeated sub-message merges, unknown fields of any wire type (groups included) and
+    known numbers with another wire type are skipped, field number 0 is rejected, varints take up to 10 bytes, minimal
+    or not, strings are validated as UTF-8."""
+    d = _pb_merge(_PB_SCHEMA[int(kind)], bytes(b), {})
+    meta = d.get("metadata")
+    return {"round": d.get("round", 0), "signature": d.get("signature", b""), "previous_signature": d.get("previous_signature", b""),
+            "randomness": d.get("randomness", b""), "metadata": meta, "beacon_id": None if meta is None else meta.get("beacon_id", "")}
+
+
+def frame_delimited(data):
+    """dh_pb_frame_delimited over bytes: ([payload], the trailing bytes that frame no record). Host only."""
+    data = bytes(data)
+    lib = _lib.load()
+    n, used = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    rc = lib.dh_pb_frame_delimited(data, len(data), None, None, 0, ctypes.byref(n), ctypes.byref(used))
+    if not n.value:
+        DeviceBoltStore._raise(rc)
+        return [], data[used.value:]
+    offs, lens = np.zeros(n.value, np.uint64), np.zeros(n.value, np.uint32)
+    DeviceBoltStore._raise(lib.dh_pb_frame_delimited(data, len(data), ctypes.c_void_p(offs.ctypes.data), ctypes.c_void_p(lens.ctypes.data),
+                                                     n.value, ctypes.byref(n), ctypes.byref(used)))
+    return [data[int(o):int(o) + int(l)] for o, l in zip(offs, lens)], data[used.value:]
+
+
+def delimited(records):
+    """The records behind varint length prefixes, one buffer."""
+    out = bytearray()
+    for r in records:
+        _pb_put_varint(out, len(r))
+        out += r
+    return bytes(out)
+
+
+def check_packets_host(kind, records, scheme, pubkey, anchor=None, beacon_id=None, verify=None):
+    """The serial host check of a run of protobuf records, the yardstick of DeviceArchive.from_packets(...).check: one
+    status byte per record (the DH_AR_* bits, bits 1 and 64 never set), as check_random_data_host gives it, plus
+    DH_AR_BEACON_ID for a record whose metadata is present with another beaconID than beacon_id (None: no comparison).
+    records: the byte strings. One that packet_from_bytes rejects gets DH_AR_INVALID and is no predecessor."""
+    verify = verify or _verify_records
+    recs = []
+    for b in records:
+        try:
+            recs.append(packet_from_bytes(kind, b))
+        except DECODE_ERRORS:
+            recs.append(False)
+    todo = [r for r in recs if r and len(r["signature"]) == scheme.sig_len]
+    verdict = dict(zip(map(id, todo), verify(scheme, pubkey, todo)))
+    out = np.zeros(len(recs), np.uint8)
+    pred = _anchor_rec(anchor)
+    for i, r in enumerate(recs):
+        if r is False:
+            out[i] = AR_INVALID
+            continue
+        out[i] = _own_bits(r, scheme.sig_len, verdict.get(id(r), False)) | _pred_bits(r, pred, scheme.chained) | _id_bits(r, beacon_id)
+        pred = r
+    return out
+
+
+def encode_beacon_packets(rounds, sigs, lens, prevs=None, prev_lens=None, beacon_id=None, delimited=False):
+    """Verifier columns on the device -> beaconToProto's BeaconPacket bytes (dh_pb_encode_device): rounds int64[n], sigs
+    uint8[n, stride], lens int32[n], prevs / prev_lens likewise or None (an unchained chain), as beacons_device gives them.
+    beacon_id None: no metadata; "": the empty sub-message. delimited: a varint length before every packet. Returns
+    (uint8 tensor on the device holding the packets back to back, int32 tensor of the packets' lengths without
+    prefix)."""
+    import torch
+    n = len(rounds)
+    bid = _id_bytes(beacon_id)
+    rounds, sigs, lens = rounds.contiguous(), sigs.contiguous(), lens.contiguous()
+    if prevs is not None:
+        prevs, prev_lens = prevs.contiguous(), prev_lens.contiguous()
+    rec_lens = torch.empty(n, dtype=torch.int32, device=rounds.device)
+    torch.cuda.synchronize()
+    ptr = lambda t: (t.data_ptr() or None) if t is not None else None  # noqa: E731
+    total = ctypes.c_size_t(0)
+
+    def call(out, cap):
+        return _lib.load().dh_pb_encode_device(
+            PB_BEACON_PACKET, ptr(rounds), ptr(sigs), sigs.shape[1] if sigs.dim() == 2 else 0, ptr(lens), ptr(prevs),
+            prevs.shape[1] if prevs is not None else 0, ptr(prev_lens), n, bid, len(bid or b""), int(bool(delimited)), out, cap,
+            ptr(rec_lens), ctypes.byref(total), None)
+    DeviceBoltStore._raise(call(None, 0))
+    out = torch.empty(total.value, dtype=torch.uint8, device=rounds.device)
+    if total.value:
+        torch.cuda.synchronize()
+        DeviceBoltStore._raise(call(out.data_ptr(), total.value))
+    return out, rec_lens
+
+
+def sync_chain_frames(store, from_round, beacon_id, window=STREAM_WINDOW, delimited=False):
+    """SyncChain's cursor loop (chain/beacon/sync_manager.go:510-525) over a DeviceBoltStore, a window of rounds at a
+    time: yields (frames uint8 tensor on the device, lengths int32 tensor) holding the BeaconPacket of every stored round
+    from from_round on, in order (round 0 stands for the first stored round). A chained store's packets carry the stored
+    previous signature: the row before in a trimmed store (NoBeaconStored when it is missing), PreviousSig in an
+    untrimmed one."""
+    rng = store.rounds_range()
+    if rng is None:
+        return
+    first, last = max(int(from_round), rng[0]), rng[1]
+    window = max(1, min(int(window), MAX_CALL_ROWS - 1))
+    while first <= last:
+        hi = min(last, first + window - 1)
+        if store.untrimmed:
+            rounds, sigs, lens, prevs, prev_lens, deferred, _m = store.beacons_device(first, hi, want_prev=store.requires_previous)
+            if int(deferred.sum()):
+                raise ValueError("rounds %d..%d hold records the device defers" % (first, hi))
+        else:
+            lo = first - 1 if store.requires_previous and first > 0 else first
+            rounds, rows, lens, _m = store.columns_device(lo, hi)
+            prevs = prev_lens = None
+            sigs = rows
+            if store.requires_previous:
+                k = int((rounds < first).sum()) if lo < first else 0  # the row of round first - 1, when stored
+                r, rw, ln = rounds[k:], rows[k:], lens[k:]
+                prevs, prev_lens = rw.new_zeros(rw.shape), ln.new_zeros(ln.shape)
+                if len(r):
+                    prevs[1:], prev_lens[1:] = rw[:-1], ln[:-1]
+                    if k:
+                        prevs[0], prev_lens[0] = rows[k - 1], lens[k - 1]
+                    linked = r.new_zeros(len(r), dtype=bool)
+                    linked[1:] = r[1:] == r[:-1] + 1
+                    linked[0] = bool(k) and int(rounds[k - 1]) + 1 == int(r[0]) or int(r[0]) == 0
+                    if not bool(linked.all()):
+                        raise NoBeaconStored("round %d: the round before it is not stored" % int(r[~linked][0]))
+                rounds, sigs, lens = r, rw.contiguous(), ln
+        if len(rounds):
+            yield encode_beacon_packets(rounds, sigs, lens, prevs, prev_lens, beacon_id, delimited)
+        first = hi + 1

@@ -384,4 +384,59 @@ def sync_from_stream(packets, scheme, pubkey, store, up_to, beacon_id="", window
         stop()
 
 
+def sync_from_frames(frames, scheme, pubkey, store, up_to, beacon_id="", resync=False, lens=None, window=1 << 20, seed=0):
+    """tryNode (/root/reference/chain/beacon/sync_manager.go:376-445) over a buffered run of raw BeaconPacket frames, the
+    bytes as they came off the wire: `frames` is a list of byte strings, or one buffer with the frames'
+    lengths in `lens` (without lens: varint-delimited). One DeviceArchive check parses and verifies every frame on the
+    device, with the store's Last() as the anchor unless `resync`; then the records are handled in order exactly as
+    sync_from_stream handles the decoded packets: stop before the first record whose metadata carries another beacon ID,
+    stop with False at the first one that does not decode or verify, Put through ChainStore (the plain write when
+    resync) with BeaconAlreadyStored / PutError handled as there. Returns (done, stored rounds)."""
+    from .store import AR_BEACON_ID, AR_INVALID, PB_BEACON_PACKET, DeviceArchive
+    stored = []
+    anchor = None
+    if not resync:
+        if not isinstance(store, ChainStore):
+            try:
+                store = ChainStore(store, scheme)
+            except NoBeaconStored:
+                return (False, stored)  # tryNode: "unable to fetch from store"
+        last = store.last()
+        anchor = (int(last.round), bytes(last.signature))
+    with DeviceArchive.from_packets(PB_BEACON_PACKET, frames, lens=lens) as ar:
+        status = ar.check(scheme, pubkey, anchor=anchor, window=window, seed=seed, beacon_id=beacon_id)
+        n = len(ar)
+        stride = max(4, (scheme.sig_len + 3) & ~3)
+        for at in range(0, n, int(window)):
+            rounds, sigs, sig_lens, prevs, prev_lens, _r, _rl, deferred = ar.beacons_device(at, int(window), sig_stride=stride, prev_stride=stride,
+                                                                                           want_rand=False)
+            rounds, sigs, prevs = rounds.cpu().numpy().view(np.uint64), sigs.cpu().numpy(), prevs.cpu().numpy()
+            prev_lens, deferred = prev_lens.cpu().numpy(), deferred.cpu().numpy()
+            for k in range(len(rounds)):
+                st = int(status[at + k])
+                if st & AR_BEACON_ID:
+                    return (False, stored)
+                if st & AR_INVALID:  # it does not decode, its signature has another length, or it does not verify
+                    return (False, stored)
+                if deferred[k]:
+                    p = ar.resolve(at + k)
+                    rnd, sig, prev = int(p["round"]), p["signature"], p["previous_signature"]
+                else:  # a verified row: the signature has the scheme's length
+                    rnd, sig = int(rounds[k]), sigs[k, :scheme.sig_len].tobytes()
+                    prev = prevs[k, :prev_lens[k]].tobytes() if prev_lens[k] <= stride else ar.resolve(at + k)["previous_signature"]
+                if resync:
+                    store.put(rnd, sig)
+                else:
+                    try:
+                        store.put(Beacon(rnd, sig, prev))
+                    except BeaconAlreadyStored:
+                        return (rnd == up_to, stored)
+                    except PutError:
+                        return (False, stored)
+                stored.append(rnd)
+                if rnd == up_to:
+                    return (True, stored)
+    return (False, stored)
+
+
 END = _END

@@ -623,6 +623,55 @@ int dh_archive_check(dh_archive* archive, int scheme, const uint8_t* pk, size_t 
 void dh_archive_close(dh_archive* archive);
 
 /*
+ * Protobuf beacon records on the device: the wire form SyncChain streams (BeaconPacket,
+ * protobuf/drand/protocol.proto:113-118) and the relays publish (PublicRandResponse, protobuf/drand/api.proto:44-52).
+ * A second front end of the dh_archive handle: the caller gives every record's length (a gossip message, a gRPC frame);
+ * nothing is framed on the device. Canonical records, what proto.Marshal writes, are decoded on the device:
+ *   BeaconPacket       := [0A L bytes] [10 V] [1A L bytes] [22 M Metadata]               prev, round, sig, metadata
+ *   PublicRandResponse := [08 V] [12 L bytes] [1A L bytes] [22 L bytes] [2A M Metadata]  round, sig, prev, randomness, metadata
+ *   Metadata           := [0A M NodeVersion] [12 L ascii] [1A L bytes]                   node_version, beaconID, chain_hash
+ *   NodeVersion        := [08 V32] [10 V32] [18 V32] [22 M ascii]                        major, minor, patch, prerelease
+ * fields in this order, each at most once, the record ending exactly at its end; minimal varints; 1 <= V < 2^64,
+ * 1 <= V32 < 2^32, L >= 1, M >= 0, ascii = bytes below 0x80. A record of 0 bytes is canonical (round 0, nothing else).
+ * Every other record, and every record above 4096 bytes, is DEFERRED, as for JSON lines.
+ *
+ * dh_archive_open_pb: records are buf[rec_off[i], rec_off[i] + rec_len[i]), offsets ascending, records not overlapping;
+ * rec_off NULL = packed from 0, the lengths summing to len. A record outside the buffer: DH_EINVAL. Size rules as
+ * dh_archive_open_ndjson. The offsets are summed on the host and uploaded: no index kernel runs, stat[6] is 0. Every
+ * other dh_archive_* call works on the handle as on a JSON-lines one (dh_archive_lines gives the payload offset and the
+ * true length); kind 1 has no randomness (lengths 0).
+ * dh_archive_kind: 0 JSON lines, DH_PB_BEACON_PACKET, DH_PB_PUBLIC_RAND.
+ * dh_archive_set_beacon_id: the ID dh_archive_check compares with (tryNode, chain/beacon/sync_manager.go:385-389): a
+ * record whose metadata is present and whose beaconID differs, byte for byte, gets DH_AR_BEACON_ID. id NULL unsets it
+ * (the state after open): the bit is never set, as on a JSON-lines handle. counts_out keeps its six entries.
+ * dh_pb_frame_delimited (host only, no device needed, off the hot path): walks varint-delimited records (minimal
+ * prefixes below 2^32) and gives each payload's offset and length. It stops at the first prefix that is malformed or
+ * whose payload runs past len and still returns DH_OK, *consumed_out telling where; a cut stream is an ordinary event.
+ * More than cap records: DH_EINVAL with *n_out = the count.
+ * dh_pb_encode_device: rows of the verifier's columns (DEVICE memory, rows 4-byte aligned, strides multiples of 4) ->
+ * beaconToProto's BeaconPacket each (chain/beacon/convert.go:9-16): previous_signature when its length is not 0, the
+ * round when not 0, the signature when its length is not 0, then metadata {beaconID}: beacon_id NULL writes none,
+ * length 0 writes 22 00. kind must be DH_PB_BEACON_PACKET. d_prevs / d_prev_lens NULL together. delimited: a varint
+ * length before every packet. d_out NULL: the sizing call, only *len_out and d_rec_len_out (nullable, DEVICE, the
+ * packet lengths without prefix) are produced. cap < *len_out: DH_EINVAL with *len_out set. A row whose packet would
+ * exceed 4096 bytes, or whose length passes its stride: DH_EINVAL naming the row. 4 GiB or more in all, or more than
+ * 16M rows: DH_EINVAL, split the call. The call waits for hip_stream first and returns with the bytes written.
+ */
+#define DH_AR_BEACON_ID 128 /* metadata present and its beaconID is not the one set with dh_archive_set_beacon_id */
+#define DH_PB_BEACON_PACKET 1
+#define DH_PB_PUBLIC_RAND 2
+int dh_archive_open_pb(int kind, const uint8_t* buf, size_t len, const uint64_t* rec_off, const uint32_t* rec_len, size_t n_rec,
+                       dh_archive** out);
+int dh_archive_kind(const dh_archive* archive);
+int dh_archive_set_beacon_id(dh_archive* archive, const uint8_t* id, size_t id_len);
+int dh_pb_frame_delimited(const uint8_t* buf, size_t len, uint64_t* off_out, uint32_t* len_out, size_t cap, size_t* n_out,
+                          size_t* consumed_out);
+int dh_pb_encode_device(int kind, const uint64_t* d_rounds, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_lens,
+                        const uint8_t* d_prevs, size_t prev_stride, const uint32_t* d_prev_lens, size_t n, const uint8_t* beacon_id,
+                        size_t beacon_id_len, int delimited, uint8_t* d_out, size_t cap, uint32_t* d_rec_len_out, size_t* len_out,
+                        void* hip_stream);
+
+/*
  * Live kernel timing: when enabled, every device stage of the verification path is bracketed by HIP
  * events on the stream it is launched on; dh_profile_read writes a JSON object
  * {"stage": {"count": c, "total_ms": t}, ...} into buf (returns the full length). dh_profile resets.
