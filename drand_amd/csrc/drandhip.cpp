@@ -2919,6 +2919,33 @@ int dh_g1_round_prep_late_debug(const uint8_t* us, const uint8_t* sigs, size_t n
   return DH_OK;
 }
 
+int dh_field_ops_debug(const uint32_t* ops, const uint32_t* in, size_t in_words, size_t n, uint32_t* out, size_t out_words) {
+  if (n == 0) return DH_OK;
+  if (!ops || !in || !out) return fail(DH_EINVAL, "null argument");
+  if (in_words < dh::FO_IN_WORDS) return fail(DH_EINVAL, "operand records of %zu words: at least %zu", in_words, dh::FO_IN_WORDS);
+  if (out_words < dh::FO_OUT_WORDS) return fail(DH_EINVAL, "result records of %zu words: at least %zu", out_words, dh::FO_OUT_WORDS);
+  if (in_words > 4096 || out_words > 4096 || n > ((size_t)1 << 24)) return fail(DH_EINVAL, "records above 4096 words or more than 2^24 lanes");
+  for (size_t i = 0; i < n; i++)
+    if (!dh::field_op_known(ops[i])) return fail(DH_EINVAL, "lane %zu: unknown field op %u", i, ops[i]);
+  lease L;
+  if (L.rc) return L.rc;
+  worker* w = L.w;
+  int rc = set_device_and_stream(w);
+  if (rc) return rc;
+  hipStream_t st = w->stream;
+  HIP_TRY(w->in_sigs.ensure(n * 4));
+  HIP_TRY(w->in_prevs.ensure(n * in_words * 4));
+  HIP_TRY(w->out_rand.ensure(n * out_words * 4));
+  HIP_TRY(hipMemcpyAsync(w->in_sigs.p, ops, n * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(w->in_prevs.p, in, n * in_words * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(w->out_rand.p, 0, n * out_words * 4, st));
+  HIP_TRY(dh::launch_field_ops(w->in_sigs.as<uint32_t>(), w->in_prevs.as<uint32_t>(), in_words, n, w->out_rand.as<uint32_t>(),
+                               out_words, st));
+  HIP_TRY(hipMemcpyAsync(out, w->out_rand.p, n * out_words * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DH_OK;
+}
+
 int dh_msm_level0_shape_debug(uint64_t* rows_per_set, uint64_t* entries, int* half_a, int* half_b) {
   if (!rows_per_set || !entries || !half_a || !half_b) return fail(DH_EINVAL, "null argument");
   *rows_per_set = g_level0.rows;

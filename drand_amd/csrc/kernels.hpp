@@ -128,6 +128,15 @@ hipError_t launch_round_g1_ride_debug(const uint8_t* u, const uint8_t* sigs, siz
 hipError_t launch_round_g1_ride_late_debug(const uint8_t* u, const uint8_t* sigs, size_t n, uint8_t* status, uint32_t* sig_aff,
                                            uint32_t* q_pts, uint32_t* s28, uint32_t* q28, uint8_t* sig_out, uint8_t* q_out,
                                            hipStream_t st);
+// test infrastructure (k_fieldops.hip, dh_field_ops_debug): lane i runs field operation ops[i] on the operand record
+// in + i in_words and writes the result record out + i out_words (zeroed by the caller). Record words a lane may touch:
+constexpr size_t FO_SCALARS = 168;    // twelve 14-limb slots, then the scalars s0 .. s7
+constexpr size_t FO_IN_WORDS = 176;
+constexpr size_t FO_OUT_FLAGS = 84;   // six 14-limb slots, then four flag words
+constexpr size_t FO_OUT_WORDS = 88;
+bool field_op_known(uint32_t op);
+hipError_t launch_field_ops(const uint32_t* ops, const uint32_t* in, size_t in_words, size_t n, uint32_t* out,
+                            size_t out_words, hipStream_t st);
 // the same hash points for messages of any length, message i = msgs[msg_off[i] .. msg_off[i + 1]) (sign.Scheme.Verify
 // in batch: xmd_any, sha256.hpp); tmp: hash_tmp_bytes(sig_g2, n)
 hipError_t launch_hash_var(int sig_g2, const uint8_t* msgs, const uint32_t* msg_off, size_t n, int dst_id, uint32_t* q_out,

@@ -565,6 +565,15 @@ int dh_g1_round_prep_late_debug(const uint8_t* us, const uint8_t* sigs, size_t n
 int dh_msm_level0_shape_debug(uint64_t* rows_per_set, uint64_t* entries, int* half_a, int* half_b);
 
 /*
+ * Test entry (test infrastructure, no product path calls it): one field-layer operation per lane, on caller-given
+ * operand words, so that the arithmetic headers can be run at the bounds they state (DESIGN.md "Field-layer op kernel"
+ * has the op table and the record layout). ops: n opcodes; in: n operand records of in_words 32-bit words (at least
+ * 176); out: n result records of out_words words (at least 88), words an operation does not write are zero. All host
+ * pointers. n = 0 succeeds; a null pointer with n > 0, an unknown opcode or records too small are DH_EINVAL.
+ */
+int dh_field_ops_debug(const uint32_t* ops, const uint32_t* in, size_t in_words, size_t n, uint32_t* out, size_t out_words);
+
+/*
  * client.RandomData JSON-lines archives on the device: the records the HTTP relays serve
  * (client/random.go:5-10, marshalled through hexjson), one per line:
  *   {"round":367,"randomness":"<64 hex>","signature":"<96|192 hex>","previous_signature":"<192 hex>"}

@@ -57,6 +57,18 @@ int main(void) {
   /* no GPU here: the pool reports a device error, cleanly */
   int rc = dh_verify_batch(3, pk, 96, rounds, sig, 48, NULL, 0, NULL, 1, v, NULL, 0);
   CHECK(rc == DH_EDEVICE || rc == DH_EKEY, "no-device path");
+  /* the field-layer test entry: refusals before any device work, n = 0, and the same device error */
+  static uint32_t fo_ops[2] = {0, 4}, fo_in[2 * 176], fo_out[2 * 88];
+  CHECK(dh_field_ops_debug(NULL, NULL, 0, 0, NULL, 0) == DH_OK, "field ops n = 0");
+  CHECK(dh_field_ops_debug(NULL, fo_in, 176, 2, fo_out, 88) == DH_EINVAL, "field ops null ops");
+  CHECK(dh_field_ops_debug(fo_ops, fo_in, 175, 2, fo_out, 88) == DH_EINVAL, "field ops short operand records");
+  CHECK(dh_field_ops_debug(fo_ops, fo_in, 176, 2, fo_out, 87) == DH_EINVAL, "field ops short result records");
+  fo_ops[1] = 10;
+  CHECK(dh_field_ops_debug(fo_ops, fo_in, 176, 2, fo_out, 88) == DH_EINVAL && strstr(dh_last_error_string(), "lane 1"),
+        "field ops unknown opcode");
+  fo_ops[1] = 4;
+  rc = dh_field_ops_debug(fo_ops, fo_in, 176, 2, fo_out, 88);
+  CHECK(rc == DH_EDEVICE || rc == DH_OK, "field ops no-device path");
   char buf[64];
   CHECK(dh_profile(1) == DH_OK && dh_profile_read(buf, sizeof buf) >= 2 && dh_profile(0) == DH_OK, "profiler");
   dh_shutdown();
