@@ -28,6 +28,8 @@ DH_AR_DEFERRED, DH_AR_NO_SIGNATURE, DH_AR_INVALID, DH_AR_RANDOMNESS = 1, 2, 4, 8
 DH_AR_SEQUENCE, DH_AR_LINK, DH_AR_PRED_DEFERRED = 16, 32, 64
 DH_AR_BEACON_ID = 128
 DH_PB_BEACON_PACKET, DH_PB_PUBLIC_RAND = 1, 2
+DH_ENC_RANDOM_DATA_JSON, DH_ENC_PUBLIC_RAND_PB = 1, 2
+DH_ENC_NEWLINE, DH_ENC_DELIMITED = 1, 2
 
 # every symbol declared in include/drandhip.h, with (restype, argtypes)
 _c = ctypes
@@ -110,6 +112,8 @@ SIGNATURES = {
     "dh_pb_frame_delimited": (_c.c_int, [_P, _c.c_size_t, _P, _P, _c.c_size_t, _P, _P]),
     "dh_pb_encode_device": (_c.c_int, [_c.c_int, _P, _P, _c.c_size_t, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P, _c.c_size_t,
                                        _c.c_int, _P, _c.c_size_t, _P, _P, _P]),
+    "dh_rand_encode_device": (_c.c_int, [_c.c_int, _P, _P, _c.c_size_t, _P, _P, _c.c_size_t, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t,
+                                         _c.c_int, _P, _c.c_size_t, _P, _P, _P]),
     "dh_profile": (_c.c_int, [_c.c_int]),
     "dh_profile_read": (_c.c_int, [_c.c_char_p, _c.c_size_t]),
     "dh_last_error_string": (_c.c_char_p, []),

@@ -160,3 +160,43 @@ def relay_s3_sync(client, get_record, upload, begin, end, window=4096, log=None)
                 continue
             uploaded.append(int(rec["round"]))
     return uploaded
+
+
+def relay_s3_sync_store(store, scheme, pubkey, upload, begin, end, window=4096, log=None):
+    """relay-s3 `sync` (cmd/relay-s3/main.go:182-195 of the reference) fed from a store file instead of a client: the
+    store (a store.DeviceBoltStore) is verified in one store.check_past pass, and every round of begin..end that is
+    stored and not faulty is uploaded as upload("public/<round>", body). The bodies are sliced from one buffer per
+    window, encoded on the device (store.encode_random_data), and are what the reference's json.Marshal really writes
+    through hexjson (main.go:13,131), store.random_data_line; relay_s3_sync keeps the base64 form of
+    marshal_random_data. As in the reference a faulty round or a failed upload is logged and skipped. Returns the
+    uploaded rounds in order."""
+    from . import store as _store
+    uploaded = []
+
+    def note(*a):
+        if log is not None:
+            log(*a)
+
+    rng = store.rounds_range()
+    if rng is None:
+        return uploaded
+    begin, end = max(int(begin), 1), min(int(end), rng[1])
+    if begin > end:
+        return uploaded
+    faulty = [r for r in store.check_past(scheme, pubkey, end) if begin <= r <= end]
+    for r in faulty:
+        note("failed to get randomness", r, "invalid beacon in the store")
+    for rounds, sigs, lens, prevs, prev_lens in _store._chain_windows(store, begin, window, end):
+        out, rec_lens = _store.encode_random_data(rounds, sigs, lens, prevs, prev_lens, keep=_store._keep_mask(rounds, faulty), newline=False)
+        buf, at = out.cpu().numpy().tobytes(), 0
+        for rnd, ln in zip(rounds.cpu().numpy().view("uint64").tolist(), rec_lens.cpu().tolist()):
+            if not ln:
+                continue
+            body, at = buf[at:at + ln], at + ln
+            try:
+                upload("public/%d" % rnd, body)
+            except Exception as e:  # noqa: BLE001 - the reference logs and continues
+                note("failed to upload randomness", e)
+                continue
+            uploaded.append(rnd)
+    return uploaded

@@ -4677,6 +4677,81 @@ int dh_pb_encode_device(int kind, const uint64_t* d_rounds, const uint8_t* d_sig
   return DH_OK;
 }
 
+int dh_rand_encode_device(int form, const uint64_t* d_rounds, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_lens,
+                          const uint8_t* d_prevs, size_t prev_stride, const uint32_t* d_prev_lens, const uint8_t* d_rands, const uint8_t* d_keep,
+                          size_t n, const uint8_t* metadata, size_t metadata_len, int flags, uint8_t* d_out, size_t cap, uint32_t* d_rec_len_out,
+                          size_t* len_out, void* hip_stream) {
+  if (!len_out) return fail(DH_EINVAL, "null argument");
+  *len_out = 0;
+  if (form != DH_ENC_RANDOM_DATA_JSON && form != DH_ENC_PUBLIC_RAND_PB)
+    return fail(DH_EINVAL, "form %d: RandomData JSON (%d) and PublicRandResponse (%d) are encoded", form, DH_ENC_RANDOM_DATA_JSON, DH_ENC_PUBLIC_RAND_PB);
+  const bool json = form == DH_ENC_RANDOM_DATA_JSON;
+  if (json && metadata) return fail(DH_EINVAL, "a RandomData record holds no metadata");
+  if (flags & ~(json ? DH_ENC_NEWLINE : DH_ENC_DELIMITED))
+    return fail(DH_EINVAL, "flags %d: DH_ENC_NEWLINE goes with the JSON form only, DH_ENC_DELIMITED with the protobuf form only", flags);
+  if (!d_prevs != !d_prev_lens) return fail(DH_EINVAL, "d_prevs and d_prev_lens are given together or not at all");
+  if (n > ARCHIVE_CALL_ROWS) return fail(DH_EINVAL, "%zu rows: at most 16M rows per call: split the call", n);
+  if (n && (!d_rounds || !d_sigs || !d_sig_lens)) return fail(DH_EINVAL, "null column");
+  if (!sig_stride || (sig_stride & 3) || sig_stride > ((size_t)1 << 20) || ((uintptr_t)d_sigs & 3) || ((uintptr_t)d_rands & 3) ||
+      (d_prevs && (!prev_stride || (prev_stride & 3) || prev_stride > ((size_t)1 << 20) || ((uintptr_t)d_prevs & 3))))
+    return fail(DH_EINVAL, "rows are 4-byte aligned with strides %zu / %zu that are positive multiples of 4, at most 1 MiB", sig_stride, prev_stride);
+  // the metadata field, the same for every row: 2A M and the caller's marshalled common.Metadata
+  std::vector<uint8_t> meta;
+  if (metadata) {
+    if (metadata_len > dh::bolt::PBWIRE_MAX_RECORD) return fail(DH_EINVAL, "metadata of %zu bytes: a record holds at most 4096", metadata_len);
+    meta.push_back(0x2A);
+    for (size_t v = metadata_len; ; v >>= 7) {
+      meta.push_back((uint8_t)(v >> 7 ? (v | 0x80) : v));
+      if (!(v >> 7)) break;
+    }
+    meta.insert(meta.end(), metadata, metadata + metadata_len);
+  }
+  int rc = ensure_device();
+  if (rc) return rc;
+  if (!n) return DH_OK;
+  HIP_TRY(hipSetDevice(g_ctx.device));
+  prof_wall p("serve_encode");
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIP_TRY(hipStreamSynchronize(st));  // the columns may be written there
+  const size_t nsum = (n + 255) / 256;
+  dbuf d_meta, frame, off, scan_tmp, sums;
+  struct free_all {
+    dbuf* b[5];
+    ~free_all() {
+      for (dbuf* x : b) x->release();
+    }
+  } guard{{&d_meta, &frame, &off, &scan_tmp, &sums}};
+  HIP_TRY(d_meta.ensure(std::max<size_t>(meta.size(), 4)));
+  HIP_TRY(frame.ensure(n * 4));
+  HIP_TRY(off.ensure((n + 1) * 4));
+  HIP_TRY(scan_tmp.ensure((n / 4096 + 2) * 4));
+  HIP_TRY(sums.ensure(nsum * sizeof(dh::pb_size_sum)));
+  if (!meta.empty()) HIP_TRY(hipMemcpyAsync(d_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, st));
+  const dh::serve_encode_in e{d_rounds, d_sigs, d_sig_lens, d_prevs, d_prev_lens, d_rands, d_keep, d_meta.as<uint8_t>(), (uint32_t)sig_stride,
+                              (uint32_t)(d_prevs ? prev_stride : 4), (uint32_t)meta.size(),
+                              json ? dh::SERVE_RANDOM_DATA_JSON : dh::SERVE_PUBLIC_RAND_PB, flags ? 1u : 0u};
+  timed_launches tl(st);
+  HIP_TRY(tl.run("k_serve_size", [&] { return dh::launch_serve_size(e, n, d_rec_len_out, frame.as<uint32_t>(), sums.as<dh::pb_size_sum>(), st); }));
+  std::vector<dh::pb_size_sum> h_sums(nsum);
+  HIP_TRY(hipMemcpyAsync(h_sums.data(), sums.p, nsum * sizeof(dh::pb_size_sum), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint64_t total = 0;
+  for (const dh::pb_size_sum& x : h_sums) {
+    if (x.first_bad != ~0ull)
+      return fail(DH_EINVAL, "row %llu: its record would exceed 4096 bytes, or a length passes its row's stride", (unsigned long long)x.first_bad);
+    total += x.bytes;
+  }
+  if (total >> 32) return fail(DH_EINVAL, "%llu bytes of records: 4 GiB or more in one call: split the call", (unsigned long long)total);
+  *len_out = (size_t)total;
+  if (!d_out) return DH_OK;
+  if (cap < total) return fail(DH_EINVAL, "%llu bytes of records, room for %zu", (unsigned long long)total, cap);
+  if (!total) return DH_OK;
+  HIP_TRY(dh::launch_scan(frame.as<uint32_t>(), n, off.as<uint32_t>(), scan_tmp.as<uint32_t>(), st));
+  HIP_TRY(tl.run("k_serve_encode", [&] { return dh::launch_serve_encode(e, n, off.as<uint32_t>(), d_out, st); }));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DH_OK;
+}
+
 int dh_archive_stat(const dh_archive* a, uint64_t out[7]) {
   if (!a || !out) return fail(DH_EINVAL, "null argument");
   memcpy(out, a->stat, sizeof a->stat);  // fixed at open

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "archive_chunk.hpp"
+#include "encode_chunk.hpp"
 #include "kernels.hpp"
 #include "pbwire.hpp"
 
@@ -124,21 +125,6 @@ __global__ __launch_bounds__(64) void k_pb_gather(int kind, const uint8_t* __res
 // ---- the encoder: verifier columns -> BeaconPacket bytes (beaconToProto, chain/beacon/convert.go:9-16 of the reference)
 
 namespace {
-__device__ __forceinline__ uint32_t varint_len(uint64_t v) {
-  uint32_t k = 1;
-  while (v >>= 7) k++;
-  return k;
-}
-__device__ __forceinline__ uint32_t put_varint(uint8_t* dst, uint32_t at, uint64_t v) {
-  while (v >> 7) {
-    dst[at++] = (uint8_t)(v | 0x80);
-    v >>= 7;
-  }
-  dst[at++] = (uint8_t)v;
-  return at;
-}
-__device__ __forceinline__ uint32_t field_len(uint32_t l) { return l ? 1 + varint_len(l) + l : 0; }
-
 struct pb_row {
   uint64_t round;
   uint32_t sig_len, prev_len;
@@ -178,20 +164,6 @@ __device__ __forceinline__ void put_frame(const pb_encode_in& e, uint64_t i, uin
     at += r.sig_len;
   }
   for (uint32_t k = 0; k < e.meta_len; k++) dst[at + k] = e.meta[k];
-}
-
-// rows [0, cnt) of a column, whose places in the chunk are dst + at[s]: lane t reads dword t of the rows (aligned) and
-// writes its bytes (LDS, any alignment)
-__device__ __forceinline__ void copy_rows(const uint8_t* __restrict__ rows, uint32_t stride, uint64_t row0, uint32_t cnt, uint8_t* dst,
-                                          const uint32_t* at, const uint32_t* lens) {
-  const uint32_t dw = stride / 4;
-  for (uint32_t t = threadIdx.x; t < cnt * dw; t += 64) {
-    const uint32_t s = t / dw, w = t - s * dw, nb = lens[s];
-    if (4 * w >= nb) continue;
-    const uint32_t word = ((const uint32_t*)rows)[(row0 + s) * dw + w];
-    const uint32_t left = nb - 4 * w < 4 ? nb - 4 * w : 4;
-    for (uint32_t k = 0; k < left; k++) dst[at[s] + 4 * w + k] = (uint8_t)(word >> (8 * k));
-  }
 }
 }  // namespace
 
@@ -258,19 +230,7 @@ __global__ __launch_bounds__(64) void k_pb_encode(const pb_encode_in e, uint64_t
   copy_rows(e.sigs, e.sig_stride, r0, cnt, img, sig_at, sig_len);
   if (e.prev_lens) copy_rows(e.prevs, e.prev_stride, r0, cnt, img, prev_at, prev_len);
   __syncthreads();
-  // LDS byte j is the output's byte a - shift + j; the region is LDS bytes [shift, end)
-  uint8_t* g = out + a - shift;  // 4-byte aligned
-  const uint32_t end = shift + (b - a);
-  const uint32_t w0 = shift ? 1 : 0, w1 = end / 4;  // the dwords wholly inside the region
-  for (uint32_t w = w0 + lane; w < w1; w += 64) ((uint32_t*)g)[w] = lds[w];
-  // the partial dwords at both ends: the head [shift, 4) when shift != 0, the tail [4 * w1, end) when it is another dword
-  // than the head (w1 >= w0; a region inside one dword is all head)
-  if (lane < 4) {
-    if (shift && lane >= shift && lane < end) g[lane] = ((const uint8_t*)lds)[lane];
-  } else if (lane < 8) {
-    const uint32_t j = 4 * w1 + (lane - 4);
-    if (w1 >= w0 && j < end) g[j] = ((const uint8_t*)lds)[j];
-  }
+  store_chunk(lds, out, a, b, shift);
 }
 
 hipError_t launch_pb_stat(int kind, const uint8_t* file, uint64_t len, const uint64_t* rec_off, const uint32_t* rec_len, size_t n, void* chunks,

@@ -412,6 +412,28 @@ hipError_t launch_pb_gather(int kind, const uint8_t* file, uint64_t len, const u
 hipError_t launch_pb_size(const pb_encode_in& e, size_t n, uint32_t* rec_len, uint32_t* frame_len, pb_size_sum* sums, hipStream_t st);
 hipError_t launch_pb_encode(const pb_encode_in& e, size_t n, const uint32_t* off, uint8_t* out, hipStream_t st);
 
+// the records a node or relay serves (k_serve.hip): verifier columns -> client.RandomData hexjson
+// objects (form 1) or PublicRandResponse messages (form 2), each with randomness = SHA-256(signature). The passes are
+// those of the BeaconPacket encoder above, pb_size_sum included. rands (nullable): 32 bytes per row, copied as given;
+// NULL: the digest of the row's sig_len signature bytes, computed in the encode pass and never stored as a column.
+// keep (nullable): a row whose byte is 0 writes nothing, has lengths 0 and is not measured. meta: the metadata field's
+// bytes (tag 0x2A included), meta_len 0 for none; form 2 only. framed: '\n' after a JSON record, a varint length
+// before a protobuf one.
+enum : uint32_t { SERVE_RANDOM_DATA_JSON = 1, SERVE_PUBLIC_RAND_PB = 2 };
+struct serve_encode_in {
+  const uint64_t* rounds;
+  const uint8_t* sigs;
+  const uint32_t* sig_lens;
+  const uint8_t* prevs;
+  const uint32_t* prev_lens;
+  const uint8_t* rands;
+  const uint8_t* keep;
+  const uint8_t* meta;
+  uint32_t sig_stride, prev_stride, meta_len, form, framed;
+};
+hipError_t launch_serve_size(const serve_encode_in& e, size_t n, uint32_t* rec_len, uint32_t* frame_len, pb_size_sum* sums, hipStream_t st);
+hipError_t launch_serve_encode(const serve_encode_in& e, size_t n, const uint32_t* off, uint8_t* out, hipStream_t st);
+
 // verifier columns -> the leaf pages of a trimmed bbolt store (k_bolt_write.hip). need: the record
 // sizes 24 + lens[i] (then launch_scan), err_word set when rounds do not ascend or a length passes the stride. pack:
 // leaves = boltw::leaf_desc records (24 B, one wave each); `image` starts at page 4 and holds every leaf extent;

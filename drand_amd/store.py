@@ -20,6 +20,9 @@ store file, plus columns(first, last) for bulk ingestion.
 * DeviceArchive — an archive of such records, one per line, parsed and checked on the device (libdrandhip
   dh_archive_*), with check_random_data_host as the serial host form of the same check and
   archive_to_trimmed_store writing a checked archive as a trimmed store file.
+* encode_random_data / encode_public_rand — the records a node or relay serves, written on the device from the
+  verifier's columns (libdrandhip dh_rand_encode_device), with random_data_frames, public_rand_frames
+  and export_random_data over a DeviceBoltStore.
 """
 import ctypes
 import json
@@ -1548,16 +1551,16 @@ def encode_beacon_packets(rounds, sigs, lens, prevs=None, prev_lens=None, beacon
     return out, rec_lens
 
 
-def sync_chain_frames(store, from_round, beacon_id, window=STREAM_WINDOW, delimited=False):
-    """SyncChain's cursor loop (chain/beacon/sync_manager.go:510-525) over a DeviceBoltStore, a window of rounds at a
-    time: yields (frames uint8 tensor on the device, lengths int32 tensor) holding the BeaconPacket of every stored round
-    from from_round on, in order (round 0 stands for the first stored round). A chained store's packets carry the stored
-    previous signature: the row before in a trimmed store (NoBeaconStored when it is missing), PreviousSig in an
-    untrimmed one."""
+def _chain_windows(store, from_round, window, up_to=None):
+    """The cursor loop the frame generators share: the stored rounds from from_round on (round 0 stands for the first
+    stored round), a window of rounds at a time, as the columns the device encoders take: yields (rounds, sigs, lens,
+    prevs, prev_lens) for every window that holds a row. A chained store's rows carry the stored previous signature: the
+    row before in a trimmed store (NoBeaconStored when it is missing), PreviousSig in an untrimmed one; prevs and
+    prev_lens are None for an unchained store. up_to: the last round wanted (default: the last stored)."""
     rng = store.rounds_range()
     if rng is None:
         return
-    first, last = max(int(from_round), rng[0]), rng[1]
+    first, last = max(int(from_round), rng[0]), rng[1] if up_to is None else min(rng[1], int(up_to))
     window = max(1, min(int(window), MAX_CALL_ROWS - 1))
     while first <= last:
         hi = min(last, first + window - 1)
@@ -1585,5 +1588,139 @@ def sync_chain_frames(store, from_round, beacon_id, window=STREAM_WINDOW, delimi
                         raise NoBeaconStored("round %d: the round before it is not stored" % int(r[~linked][0]))
                 rounds, sigs, lens = r, rw.contiguous(), ln
         if len(rounds):
-            yield encode_beacon_packets(rounds, sigs, lens, prevs, prev_lens, beacon_id, delimited)
+            yield rounds, sigs, lens, prevs, prev_lens
         first = hi + 1
+
+
+def sync_chain_frames(store, from_round, beacon_id, window=STREAM_WINDOW, delimited=False):
+    """SyncChain's cursor loop (chain/beacon/sync_manager.go:510-525) over a DeviceBoltStore, a window of rounds at a
+    time: yields (frames uint8 tensor on the device, lengths int32 tensor) holding the BeaconPacket of every stored round
+    from from_round on, in order (round 0 stands for the first stored round). A chained store's packets carry the stored
+    previous signature: the row before in a trimmed store (NoBeaconStored when it is missing), PreviousSig in an
+    untrimmed one."""
+    for rounds, sigs, lens, prevs, prev_lens in _chain_windows(store, from_round, window):
+        yield encode_beacon_packets(rounds, sigs, lens, prevs, prev_lens, beacon_id, delimited)
+
+
+# ---- the records a node or relay serves, encoded on the device (DESIGN.md §28): client.RandomData through hexjson
+# (http/server.go:336-342, cmd/relay-s3/main.go:127-141) and PublicRandResponse (core/convert.go:15-22)
+
+def metadata_bytes(md):
+    """proto.Marshal of common.Metadata from the dict packet_bytes takes under "metadata" ({beacon_id, chain_hash,
+    node_version}): the body that follows a record's metadata tag and length. None (no metadata) gives None."""
+    if md is None:
+        return None
+    out = bytearray()
+    _pb_put(out, _PB_METADATA, md)
+    return bytes(out)
+
+
+def _encode_rand(form, rounds, sigs, lens, prevs, prev_lens, rands, keep, metadata, flags):
+    import torch
+    n = len(rounds)
+    rounds, sigs, lens = rounds.contiguous(), sigs.contiguous(), lens.contiguous()
+    if prevs is not None:
+        prevs, prev_lens = prevs.contiguous(), prev_lens.contiguous()
+    if rands is not None:
+        rands = rands.contiguous()
+        if rands.dtype != torch.uint8 or rands.numel() != 32 * n:
+            raise ValueError("rands: uint8 rows of 32 bytes, one per row")
+    if keep is not None:
+        keep = keep.contiguous()
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+        if keep.dtype != torch.uint8 or keep.numel() != n:
+            raise ValueError("keep: one byte per row")
+    if metadata is not None and not isinstance(metadata, (bytes, bytearray)):
+        metadata = metadata_bytes(metadata)
+    md = bytes(metadata) if metadata is not None else None
+    rec_lens = torch.empty(n, dtype=torch.int32, device=rounds.device)
+    torch.cuda.synchronize()
+    ptr = lambda t: (t.data_ptr() or None) if t is not None else None  # noqa: E731
+    total = ctypes.c_size_t(0)
+
+    def call(out, cap):
+        return _lib.load().dh_rand_encode_device(
+            form, ptr(rounds), ptr(sigs), sigs.shape[1] if sigs.dim() == 2 else 0, ptr(lens), ptr(prevs),
+            prevs.shape[1] if prevs is not None else 0, ptr(prev_lens), ptr(rands), ptr(keep), n, md, len(md or b""), flags, out, cap,
+            ptr(rec_lens), ctypes.byref(total), None)
+    DeviceBoltStore._raise(call(None, 0))
+    out = torch.empty(total.value, dtype=torch.uint8, device=rounds.device)
+    if total.value:
+        torch.cuda.synchronize()
+        DeviceBoltStore._raise(call(out.data_ptr(), total.value))
+    return out, rec_lens
+
+
+def encode_random_data(rounds, sigs, lens, prevs=None, prev_lens=None, rands=None, keep=None, newline=True):
+    """Verifier columns on the device -> client.RandomData hexjson objects (dh_rand_encode_device), each byte for byte
+    random_data_line of its row; the columns as for encode_beacon_packets. rands None: every record carries SHA-256 of
+    its signature, computed on the device; else uint8[n, 32] copied as given (verify's randomness column). keep None:
+    every row is written; else uint8[n] / bool[n], a row whose byte is 0 writes nothing (verify's verdict column).
+    newline: b"\\n" after every record written. Returns (uint8 tensor on the device holding the records back to back,
+    int32 tensor of the records' lengths without newline, 0 for a row left out)."""
+    return _encode_rand(_lib.DH_ENC_RANDOM_DATA_JSON, rounds, sigs, lens, prevs, prev_lens, rands, keep, None,
+                        _lib.DH_ENC_NEWLINE if newline else 0)
+
+
+def encode_public_rand(rounds, sigs, lens, prevs=None, prev_lens=None, rands=None, keep=None, metadata=None, delimited=False):
+    """Verifier columns on the device -> PublicRandResponse messages (dh_rand_encode_device), each byte for byte
+    packet_bytes(PB_PUBLIC_RAND, ...) of its row. metadata: None (no field), the dict packet_bytes takes, or the
+    marshalled common.Metadata bytes (b"" writes the empty sub-message). delimited: a varint length before every record
+    written. Everything else as encode_random_data."""
+    return _encode_rand(_lib.DH_ENC_PUBLIC_RAND_PB, rounds, sigs, lens, prevs, prev_lens, rands, keep, metadata,
+                        _lib.DH_ENC_DELIMITED if delimited else 0)
+
+
+def _keep_mask(rounds, skip):
+    """The keep column for `rounds` (device, the u64 bit pattern) with the rounds of `skip` left out, built on the
+    device; None when nothing is skipped."""
+    import torch
+    skip = np.array(sorted(set(int(r) for r in skip)), dtype=np.uint64)
+    if not len(skip):
+        return None
+    return (~torch.isin(rounds, torch.from_numpy(skip.view(np.int64)).to(rounds.device))).to(torch.uint8)
+
+
+def random_data_frames(store, from_round=1, window=STREAM_WINDOW, skip=(), newline=True, up_to=None):
+    """The RandomData hexjson object of every stored round from from_round on (up to up_to, default the last), a window
+    of rounds at a time, over a DeviceBoltStore of either format: yields (records uint8 tensor on the device, lengths
+    int32 tensor) per window, with the windows and previous signatures of sync_chain_frames. skip: rounds to leave out
+    (their length is 0, they write nothing)."""
+    for rounds, sigs, lens, prevs, prev_lens in _chain_windows(store, from_round, window, up_to):
+        yield encode_random_data(rounds, sigs, lens, prevs, prev_lens, keep=_keep_mask(rounds, skip), newline=newline)
+
+
+def public_rand_frames(store, from_round, metadata=None, window=STREAM_WINDOW, skip=(), delimited=False, up_to=None):
+    """PublicRand / PublicRandStream's backlog (core/drand_beacon_public.go:67-119) over a DeviceBoltStore: the
+    PublicRandResponse of every stored round from from_round on, yielded as random_data_frames yields its records.
+    metadata: None, the dict packet_bytes takes, or the marshalled common.Metadata bytes."""
+    md = metadata_bytes(metadata) if isinstance(metadata, dict) else metadata
+    for rounds, sigs, lens, prevs, prev_lens in _chain_windows(store, from_round, window, up_to):
+        yield encode_public_rand(rounds, sigs, lens, prevs, prev_lens, keep=_keep_mask(rounds, skip), metadata=md, delimited=delimited)
+
+
+def export_random_data(store, path, scheme=None, pubkey=None, up_to=None, window=STREAM_WINDOW):
+    """A DeviceBoltStore written out as a RandomData JSON-lines archive: one hexjson object and b"\\n" per stored round
+    from round 1 up to up_to (default the last). With a scheme and key store.check_past runs first and the faulty rounds
+    are left out. The windows stream into path + ".tmp", which then replaces path. Returns {"records", "bytes",
+    "faulty"}."""
+    rng = store.rounds_range()
+    last = rng[1] if rng else 0
+    up_to = last if up_to is None else min(int(up_to), last)
+    faulty = []
+    if scheme is not None and rng:
+        faulty = [int(r) for r in store.check_past(scheme, pubkey, up_to)]
+    records = nbytes = 0
+    tmp = path + ".tmp"
+    try:
+        with open(tmp, "wb") as f:
+            for out, rec_lens in random_data_frames(store, 1, window, skip=faulty, up_to=up_to):
+                f.write(out.cpu().numpy().tobytes())
+                records += int((rec_lens > 0).sum())
+                nbytes += int(out.numel())
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.unlink(tmp)
+    return {"records": records, "bytes": nbytes, "faulty": faulty}

@@ -681,6 +681,39 @@ int dh_pb_encode_device(int kind, const uint64_t* d_rounds, const uint8_t* d_sig
                         void* hip_stream);
 
 /*
+ * The records a node or relay serves to the public, encoded on the device. Rows of the verifier's
+ * columns (DEVICE memory, as for dh_pb_encode_device) -> one record each, carrying randomness = SHA-256(signature)
+ * (crypto.RandomnessFromSignature):
+ *   DH_ENC_RANDOM_DATA_JSON  client.RandomData through hexjson (http/server.go:336-342, cmd/relay-s3/main.go:127-141):
+ *                            {"round":D,"randomness":"H","signature":"H","previous_signature":"H"}, lowercase hex
+ *   DH_ENC_PUBLIC_RAND_PB    proto.Marshal of drand.PublicRandResponse (core/convert.go:15-22):
+ *                            [08 V] [12 L sig] [1A L prev] [22 L rand] [2A M metadata], minimal varints
+ * fields in this order, each left out when empty (round 0, a length of 0).
+ * d_rands NULL: every record carries SHA-256 of its sig_len signature bytes (of the empty string for length 0), computed
+ * in the encode kernel and stored nowhere else; else rows of 32 bytes (4-byte aligned), copied as given:
+ * dh_verify_batch_device's d_rand_out. d_keep (nullable, one byte per row): a row whose byte is 0 writes nothing, no
+ * newline and no prefix, has d_rec_len_out 0 and is neither measured nor refused; dh_verify_batch_device's
+ * d_verdict_out plugs in. metadata (protobuf only; not NULL with the JSON form: DH_EINVAL): the caller's marshalled
+ * common.Metadata, at most 4096 bytes, copied opaquely after 2A and its length; NULL writes no field, length 0 writes
+ * 2A 00. flags: DH_ENC_NEWLINE (JSON only) writes '\n' after every record, DH_ENC_DELIMITED (protobuf only) a minimal
+ * varint length before every record; the other combination or an unknown bit: DH_EINVAL.
+ * Everything else is dh_pb_encode_device's: d_prevs / d_prev_lens NULL together, rows 4-byte aligned, strides positive
+ * multiples of 4 up to 1 MiB, d_out NULL the sizing call, cap < *len_out DH_EINVAL with *len_out set, a kept row whose
+ * record would exceed 4096 bytes (without prefix and newline) or whose length passes its stride DH_EINVAL naming the
+ * row, 4 GiB or more in all or more than 16M rows DH_EINVAL (split the call), n == 0 DH_OK with length 0. The argument
+ * refusals are decided before the device is touched. The call waits for hip_stream first and returns with the bytes
+ * written. dh_profile stage: serve_encode (k_serve_size, k_serve_encode).
+ */
+#define DH_ENC_RANDOM_DATA_JSON 1
+#define DH_ENC_PUBLIC_RAND_PB 2
+#define DH_ENC_NEWLINE 1
+#define DH_ENC_DELIMITED 2
+int dh_rand_encode_device(int form, const uint64_t* d_rounds, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_lens,
+                          const uint8_t* d_prevs, size_t prev_stride, const uint32_t* d_prev_lens, const uint8_t* d_rands, const uint8_t* d_keep,
+                          size_t n, const uint8_t* metadata, size_t metadata_len, int flags, uint8_t* d_out, size_t cap,
+                          uint32_t* d_rec_len_out, size_t* len_out, void* hip_stream);
+
+/*
  * Live kernel timing: when enabled, every device stage of the verification path is bracketed by HIP
  * events on the stream it is launched on; dh_profile_read writes a JSON object
  * {"stage": {"count": c, "total_ms": t}, ...} into buf (returns the full length). dh_profile resets.
