@@ -19,3 +19,10 @@ from .scheme import (  # noqa: F401
     hash_to_curve,
 )
 from .chain import Beacon, randomness_from_signature  # noqa: F401
+from .store import (  # noqa: F401,E402
+    assemble_host,
+    assemble_columns,
+    assemble_archives,
+    assemble_to_trimmed_store,
+)
+from .sync import sync_from_sources  # noqa: F401,E402

@@ -30,6 +30,8 @@ DH_AR_BEACON_ID = 128
 DH_PB_BEACON_PACKET, DH_PB_PUBLIC_RAND = 1, 2
 DH_ENC_RANDOM_DATA_JSON, DH_ENC_PUBLIC_RAND_PB = 1, 2
 DH_ENC_NEWLINE, DH_ENC_DELIMITED = 1, 2
+DH_AS_CHOSEN, DH_AS_DUPLICATE, DH_AS_INVALID, DH_AS_STALE, DH_AS_SKIPPED, DH_AS_CONFLICT = 1, 2, 4, 8, 16, 32
+DH_AS_GAP, DH_AS_LINK = 1, 2
 
 # every symbol declared in include/drandhip.h, with (restype, argtypes)
 _c = ctypes
@@ -114,6 +116,10 @@ SIGNATURES = {
                                        _c.c_int, _P, _c.c_size_t, _P, _P, _P]),
     "dh_rand_encode_device": (_c.c_int, [_c.c_int, _P, _P, _c.c_size_t, _P, _P, _c.c_size_t, _P, _P, _P, _c.c_size_t, _P, _c.c_size_t,
                                          _c.c_int, _P, _c.c_size_t, _P, _P, _P]),
+    "dh_assemble_device": (_c.c_int, [_c.c_int, _c.c_char_p, _c.c_size_t, _P, _P, _c.c_size_t, _P, _P, _c.c_size_t, _P, _P, _c.c_size_t, _P, _P,
+                                      _c.c_size_t, _P, _c.c_size_t, _c.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _c.c_size_t, _P,
+                                      _P, _P]),
+    "dh_sort_rounds_debug": (_c.c_int, [_P, _c.c_size_t, _P]),
     "dh_profile": (_c.c_int, [_c.c_int]),
     "dh_profile_read": (_c.c_int, [_c.c_char_p, _c.c_size_t]),
     "dh_last_error_string": (_c.c_char_p, []),

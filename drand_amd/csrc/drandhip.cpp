@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "../../include/drandhip.h"
+#include "assemble.hpp"
 #include "bolt.hpp"
 #include "bolt_write.hpp"
 #include "kernels.hpp"
@@ -4941,6 +4942,283 @@ int dh_archive_check(dh_archive* a, int scheme, const uint8_t* pk, size_t pk_len
   }
   counts_out[0] = n_rec;
   return counts_out[1] ? DH_DEFERRED : DH_OK;
+}
+
+}  // extern "C"
+
+// ---- one chain from unordered candidate columns (k_assemble.hip): cut the skipped and stale
+// candidates, sort the rest by round (stable, so a run keeps the input order), collapse the copies inside a run, verify
+// each representative once through dh_verify_batch_device, pick the first valid representative per round
+
+namespace {
+
+struct dbuf_pool {  // a call's own buffers and stream: nothing is shared between calls
+  std::vector<dbuf*> bufs;
+  hipStream_t st = nullptr;
+  ~dbuf_pool() {
+    for (dbuf* b : bufs) b->release();
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+// (keys, idx)[0, n) sorted by key, stably, through (keys_alt, idx_alt); *in_alt: the result lies in the alt pair. A
+// pass whose digit is the same in every key moves nothing and is skipped. Ends with the stream idle only when n < 2.
+int sort_pairs(uint64_t* keys, uint32_t* idx, uint64_t* keys_alt, uint32_t* idx_alt, size_t n, dbuf& cnt, dbuf& off, dbuf& scan_tmp, dbuf& orand,
+               hipStream_t st, bool* in_alt) {
+  *in_alt = false;
+  if (n < 2) return DH_OK;
+  uint64_t h[2] = {0, ~0ull};
+  HIP_TRY(orand.ensure(16));
+  HIP_TRY(hipMemcpyAsync(orand.p, h, 16, hipMemcpyHostToDevice, st));
+  timed_launches tl(st);
+  HIP_TRY(tl.run("k_sort_orand", [&] { return dh::launch_sort_orand(keys, n, orand.as<uint64_t>(), st); }));
+  HIP_TRY(hipStreamSynchronize(st));  // `h` was read by then
+  HIP_TRY(hipMemcpyAsync(h, orand.p, 16, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  const uint64_t varies = h[0] ^ h[1];
+  const size_t nk = 256 * ((n + dh::SORT_TILE - 1) / dh::SORT_TILE);
+  HIP_TRY(cnt.ensure(nk * 4));
+  HIP_TRY(off.ensure((nk + 1) * 4));
+  HIP_TRY(scan_tmp.ensure((nk / 4096 + 2) * 4));
+  for (uint32_t shift = 0; shift < 64; shift += 8) {
+    if (!((varies >> shift) & 255)) continue;
+    HIP_TRY(tl.run("k_sort_pass", [&] {  // histogram, scan and scatter of one digit
+      return dh::launch_sort_pass(keys, idx, n, shift, cnt.as<uint32_t>(), off.as<uint32_t>(), scan_tmp.as<uint32_t>(), keys_alt, idx_alt, st);
+    }));
+    std::swap(keys, keys_alt);
+    std::swap(idx, idx_alt);
+    *in_alt = !*in_alt;
+  }
+  return DH_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dh_sort_rounds_debug(const uint64_t* keys, size_t n, uint32_t* perm_out) {
+  if (n == 0) return DH_OK;
+  if (!keys || !perm_out) return fail(DH_EINVAL, "null argument");
+  if (n > ARCHIVE_CALL_ROWS) return fail(DH_EINVAL, "%zu keys: at most 16M per call", n);
+  int rc = ensure_device();
+  if (rc) return rc;
+  dbuf k[2], ix[2], cnt, off, scan_tmp, orand;
+  dbuf_pool pool{{&k[0], &k[1], &ix[0], &ix[1], &cnt, &off, &scan_tmp, &orand}};
+  HIP_TRY(hipStreamCreateWithFlags(&pool.st, hipStreamNonBlocking));
+  hipStream_t st = pool.st;
+  for (int i = 0; i < 2; i++) {
+    HIP_TRY(k[i].ensure(n * 8));
+    HIP_TRY(ix[i].ensure(n * 4));
+  }
+  HIP_TRY(hipMemcpyAsync(k[0].p, keys, n * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(dh::launch_iota(ix[0].as<uint32_t>(), n, st));
+  bool in_alt = false;
+  if ((rc = sort_pairs(k[0].as<uint64_t>(), ix[0].as<uint32_t>(), k[1].as<uint64_t>(), ix[1].as<uint32_t>(), n, cnt, off, scan_tmp, orand, st,
+                       &in_alt)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(perm_out, ix[in_alt].p, n * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DH_OK;
+}
+
+int dh_assemble_device(int scheme, const uint8_t* pk, size_t pk_len, const uint64_t* d_rounds, const uint8_t* d_sigs, size_t sig_stride,
+                       const uint32_t* d_sig_lens, const uint8_t* d_prevs, size_t prev_stride, const uint32_t* d_prev_lens, const uint8_t* d_skip,
+                       size_t n, const uint64_t* anchor_round, const uint8_t* anchor_sig, size_t anchor_sig_len, const uint64_t* up_to,
+                       size_t window, uint64_t seed, uint64_t* d_rounds_out, uint8_t* d_sigs_out, uint32_t* d_sig_lens_out, uint8_t* d_prevs_out,
+                       uint32_t* d_prev_lens_out, uint32_t* d_src_out, uint8_t* d_flags_out, size_t* m_out, uint8_t* status_out,
+                       uint64_t* gap_first_out, uint64_t* gap_last_out, size_t gap_cap, size_t* n_gaps_out, uint64_t counts_out[10],
+                       void* hip_stream) {
+  if (!pk || !m_out || !n_gaps_out || !counts_out) return fail(DH_EINVAL, "null argument");
+  *m_out = 0;
+  *n_gaps_out = 0;
+  memset(counts_out, 0, 10 * sizeof(uint64_t));
+  if (scheme < 0 || scheme > 3) return fail(DH_EINVAL, "unknown scheme %d", scheme);
+  if (!window) return fail(DH_EINVAL, "window must be >= 1");
+  if (n > ARCHIVE_CALL_ROWS) return fail(DH_EINVAL, "%zu candidates: at most 16M rows per call", n);
+  const bool chained = scheme == DH_SCHEME_CHAINED;
+  if (!d_prevs != !d_prev_lens) return fail(DH_EINVAL, "d_prevs and d_prev_lens are given together or not at all");
+  if (!d_prevs_out != !d_prev_lens_out) return fail(DH_EINVAL, "d_prevs_out and d_prev_lens_out are given together or not at all");
+  if (!chained) d_prevs = nullptr, d_prev_lens = nullptr;  // the unchained schemes read no previous signature
+  if (chained && n && !d_prevs) return fail(DH_EINVAL, "the chained scheme needs the previous_signature columns");
+  if (!chained && d_prevs_out) return fail(DH_EINVAL, "previous_signature output columns go with the chained scheme only");
+  if (!sig_stride || (sig_stride & 3) || sig_stride > ((size_t)1 << 20) || ((uintptr_t)d_sigs & 3) || ((uintptr_t)d_sigs_out & 3) ||
+      (d_prevs && (!prev_stride || (prev_stride & 3) || prev_stride > ((size_t)1 << 20) || ((uintptr_t)d_prevs & 3) || ((uintptr_t)d_prevs_out & 3))))
+    return fail(DH_EINVAL, "rows are 4-byte aligned with strides %zu / %zu that are positive multiples of 4, at most 1 MiB", sig_stride, prev_stride);
+  if (n && (!d_rounds || !d_sigs || !d_sig_lens)) return fail(DH_EINVAL, "null column");
+  if (n && (!d_rounds_out || !d_sigs_out || !d_sig_lens_out || !d_src_out || !d_flags_out || !status_out)) return fail(DH_EINVAL, "null output");
+  if (anchor_round && anchor_sig_len && !anchor_sig) return fail(DH_EINVAL, "null anchor signature");
+  if (anchor_sig_len > ((size_t)1 << 20)) return fail(DH_EINVAL, "anchor signature of %zu bytes: at most 1 MiB", anchor_sig_len);
+  if (gap_cap && (!gap_first_out || !gap_last_out)) return fail(DH_EINVAL, "null gap arrays");
+  const uint32_t want = (uint32_t)dh_sig_len(scheme);
+  const char* env = getenv("DRANDHIP_ASSEMBLE_DEDUPE");  // read at every call: 0 makes every candidate a representative
+  const bool dedupe = !(env && env[0] == '0' && !env[1]);
+  window = std::min(window, ARCHIVE_CALL_ROWS);
+  int rc = ensure_device();
+  if (rc) return rc;
+  if (hip_stream) HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));  // the columns may be written there
+  dbuf status, live, pos, k[2], ix[2], cnt, off, scan_tmp, orand, run_start, rep, rpos, rep_cand, chosen, opos, v_rounds, v_sigs, v_prevs,
+      v_prev_lens, verdict, anchor, gaps;
+  dbuf_pool pool{{&status, &live, &pos, &k[0], &k[1], &ix[0], &ix[1], &cnt, &off, &scan_tmp, &orand, &run_start, &rep, &rpos, &rep_cand,
+                  &chosen, &opos, &v_rounds, &v_sigs, &v_prevs, &v_prev_lens, &verdict, &anchor, &gaps}};
+  HIP_TRY(hipStreamCreateWithFlags(&pool.st, hipStreamNonBlocking));
+  hipStream_t st = pool.st;
+  const dh::assemble::cols c{d_rounds, d_sigs, d_sig_lens, d_prevs, d_prev_lens, d_skip, (uint32_t)sig_stride, (uint32_t)(d_prevs ? prev_stride : 4)};
+  const dh::assemble::bounds b{anchor_round ? *anchor_round : 0, up_to ? *up_to : 0, anchor_round ? 1u : 0u, up_to ? 1u : 0u};
+  size_t m = 0, n_runs = 0, n_rep = 0, n_out = 0;
+  bool in_alt = false;
+  HIP_TRY(scan_tmp.ensure(((std::max(n, (size_t)256 * ((n + dh::SORT_TILE - 1) / dh::SORT_TILE)) + 2) / 4096 + 2) * 4));
+  {
+    prof_wall p("assemble_sort");
+    HIP_TRY(status.ensure(n));
+    HIP_TRY(live.ensure((n + 2) * 4));
+    HIP_TRY(pos.ensure((n + 2) * 4));
+    HIP_TRY(dh::launch_assemble_pre(c, n, b, status.as<uint8_t>(), live.as<uint32_t>(), st));
+    if (n) {
+      HIP_TRY(dh::launch_scan(live.as<uint32_t>(), n, pos.as<uint32_t>(), scan_tmp.as<uint32_t>(), st));
+      uint32_t total = 0;
+      HIP_TRY(hipMemcpyAsync(&total, pos.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      m = total;
+    }
+    for (int i = 0; i < 2; i++) {
+      HIP_TRY(k[i].ensure(m * 8));
+      HIP_TRY(ix[i].ensure(m * 4));
+    }
+    if (m) HIP_TRY(dh::launch_assemble_cut(d_rounds, n, pos.as<uint32_t>(), k[0].as<uint64_t>(), ix[0].as<uint32_t>(), st));
+    if ((rc = sort_pairs(k[0].as<uint64_t>(), ix[0].as<uint32_t>(), k[1].as<uint64_t>(), ix[1].as<uint32_t>(), m, cnt, off, scan_tmp, orand, st,
+                         &in_alt)))
+      return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  const uint64_t* keys = k[in_alt].as<uint64_t>();
+  const uint32_t* idx = ix[in_alt].as<uint32_t>();
+  uint32_t* flag = live.as<uint32_t>();   // heads, then representatives, then chosen rows, then gaps: m + 1 words at most
+  uint32_t* runs = pos.as<uint32_t>();    // the scanned heads: the cut has read pos by now (stream order)
+  {
+    prof_wall p("assemble_class");
+    HIP_TRY(dh::launch_assemble_heads(keys, m, flag, st));
+    if (m) {
+      HIP_TRY(dh::launch_scan(flag, m, runs, scan_tmp.as<uint32_t>(), st));
+      uint32_t total = 0;
+      HIP_TRY(hipMemcpyAsync(&total, runs + m, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      n_runs = total;
+    }
+    HIP_TRY(run_start.ensure(n_runs * 4));
+    HIP_TRY(rep.ensure(m * 4));
+    HIP_TRY(rpos.ensure((m + 1) * 4));
+    HIP_TRY(dh::launch_assemble_runs(runs, m, run_start.as<uint32_t>(), st));
+    HIP_TRY(dh::launch_assemble_class(c, idx, runs, run_start.as<uint32_t>(), m, dedupe, rep.as<uint32_t>(), flag, st));
+    if (m) {
+      HIP_TRY(dh::launch_scan(flag, m, rpos.as<uint32_t>(), scan_tmp.as<uint32_t>(), st));
+      uint32_t total = 0;
+      HIP_TRY(hipMemcpyAsync(&total, rpos.as<uint32_t>() + m, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      n_rep = total;
+    }
+    HIP_TRY(rep_cand.ensure(n_rep * 4));
+    HIP_TRY(dh::launch_assemble_reps(idx, rpos.as<uint32_t>(), m, rep_cand.as<uint32_t>(), st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  {
+    prof_wall p("assemble_verify");
+    // the representatives in the verifier's columns, `window` rows at a time, as dh_archive_check verifies a window:
+    // the chained scheme against each candidate's OWN previous_signature; a row of another length is left zero and its
+    // verdict is not read
+    const size_t wmax = std::min(window, n_rep);
+    const dh::assemble_verify_cols v{nullptr, nullptr, nullptr, nullptr, (uint32_t)std::max(sig_stride, ((size_t)want + 3) & ~(size_t)3),
+                                     (uint32_t)(d_prevs ? prev_stride : 4)};
+    HIP_TRY(v_rounds.ensure(wmax * 8));
+    HIP_TRY(v_sigs.ensure(wmax * (size_t)v.sig_stride));
+    if (chained) {
+      HIP_TRY(v_prevs.ensure(wmax * (size_t)v.prev_stride));
+      HIP_TRY(v_prev_lens.ensure(wmax * 4));
+    }
+    HIP_TRY(verdict.ensure(n_rep));
+    dh::assemble_verify_cols vw = v;
+    vw.rounds = v_rounds.as<uint64_t>();
+    vw.sigs = v_sigs.as<uint8_t>();
+    vw.prevs = v_prevs.as<uint8_t>();
+    vw.prev_lens = v_prev_lens.as<uint32_t>();
+    for (size_t at = 0; at < n_rep; at += window) {
+      const size_t kk = std::min(window, n_rep - at);
+      HIP_TRY(dh::launch_assemble_gather(c, rep_cand.as<uint32_t>() + at, kk, want, vw, st));
+      rc = dh_verify_batch_device(scheme, pk, pk_len, vw.rounds, vw.sigs, vw.sig_stride, chained ? vw.prevs : nullptr, vw.prev_stride,
+                                  chained ? vw.prev_lens : nullptr, kk, verdict.as<uint8_t>() + at, nullptr, seed, st, nullptr);
+      if (rc) return rc;
+    }
+  }
+  uint64_t n_gaps = 0;
+  std::vector<uint8_t> h_flags;
+  std::vector<uint64_t> h_gaps;
+  {
+    prof_wall p("assemble_select");
+    HIP_TRY(chosen.ensure(n_runs * 4));
+    HIP_TRY(opos.ensure((n + 3) * 4));
+    HIP_TRY(dh::launch_assemble_pick(c, idx, run_start.as<uint32_t>(), n_runs, m, rpos.as<uint32_t>(), verdict.as<uint8_t>(), want,
+                                     chosen.as<uint32_t>(), st));
+    HIP_TRY(dh::launch_assemble_select(c, idx, runs, run_start.as<uint32_t>(), rep.as<uint32_t>(), rpos.as<uint32_t>(), verdict.as<uint8_t>(), chosen.as<uint32_t>(), m,
+                                       want, status.as<uint8_t>(), flag, st));
+    if (n) HIP_TRY(hipMemcpyAsync(status_out, status.p, n, hipMemcpyDeviceToHost, st));
+    if (m) {
+      HIP_TRY(dh::launch_scan(flag, m, opos.as<uint32_t>(), scan_tmp.as<uint32_t>(), st));
+      uint32_t total = 0;
+      HIP_TRY(hipMemcpyAsync(&total, opos.as<uint32_t>() + m, 4, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+      n_out = total;
+    }
+    const dh::assemble_out o{d_rounds_out, d_sigs_out, d_sig_lens_out, d_prevs_out, d_prev_lens_out, d_src_out, d_flags_out};
+    HIP_TRY(dh::launch_assemble_emit(c, idx, opos.as<uint32_t>(), m, o, st));
+    // the anchor as row -1: {round, signature length, the signature from byte 16}; always allocated, so that the link
+    // kernel's uniform loads have an address
+    const size_t a_len = anchor_round ? anchor_sig_len : 0;
+    std::vector<uint64_t> h_anchor(2 + (a_len + 7) / 8, 0);
+    h_anchor[0] = b.anchor_round;
+    h_anchor[1] = a_len;
+    if (a_len) memcpy(h_anchor.data() + 2, anchor_sig, a_len);
+    HIP_TRY(anchor.ensure(h_anchor.size() * 8));
+    HIP_TRY(hipMemcpyAsync(anchor.p, h_anchor.data(), h_anchor.size() * 8, hipMemcpyHostToDevice, st));
+    uint32_t* goff = opos.as<uint32_t>();  // the emit has read opos by then (stream order)
+    HIP_TRY(dh::launch_assemble_link(c, o, n_out, b, anchor.as<uint64_t>(), chained, flag, st));
+    HIP_TRY(dh::launch_scan(flag, n_out + 1, goff, scan_tmp.as<uint32_t>(), st));
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, goff + n_out + 1, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // h_anchor was read by then
+    n_gaps = total;
+    if (n_gaps) {
+      HIP_TRY(gaps.ensure(n_gaps * 16));
+      HIP_TRY(dh::launch_assemble_gaps(o, n_out, b, goff, gaps.as<uint64_t>(), gaps.as<uint64_t>() + n_gaps, st));
+      h_gaps.resize(2 * n_gaps);
+      HIP_TRY(hipMemcpyAsync(h_gaps.data(), gaps.p, n_gaps * 16, hipMemcpyDeviceToHost, st));
+    }
+    h_flags.resize(n_out);
+    if (n_out) HIP_TRY(hipMemcpyAsync(h_flags.data(), d_flags_out, n_out, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  }
+  *m_out = n_out;
+  *n_gaps_out = (size_t)n_gaps;
+  counts_out[0] = n;
+  counts_out[3] = n_rep;
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t s = status_out[i];
+    counts_out[1] += s & DH_AS_SKIPPED ? 1 : 0;
+    counts_out[2] += s & DH_AS_STALE ? 1 : 0;
+    counts_out[4] += s & DH_AS_INVALID ? 1 : 0;
+    counts_out[5] += s & DH_AS_DUPLICATE ? 1 : 0;
+    counts_out[6] += s & DH_AS_CONFLICT ? 1 : 0;
+    counts_out[7] += s & DH_AS_CHOSEN ? 1 : 0;
+  }
+  for (uint64_t g = 0; g < n_gaps; g++) {
+    const uint64_t span = h_gaps[n_gaps + g] - h_gaps[g] + 1;  // 0: all 2^64 rounds, which no u64 range holds
+    counts_out[8] = counts_out[8] + span < span ? ~0ull : counts_out[8] + span;
+    if (g < gap_cap) {
+      gap_first_out[g] = h_gaps[g];
+      gap_last_out[g] = h_gaps[n_gaps + g];
+    }
+  }
+  for (uint8_t f : h_flags) counts_out[9] += f & DH_AS_LINK ? 1 : 0;
+  if (n_gaps > gap_cap) return fail(DH_EINVAL, "%llu gaps, room for %zu", (unsigned long long)n_gaps, gap_cap);
+  return DH_OK;
 }
 
 }  // extern "C"

@@ -491,6 +491,64 @@ hipError_t launch_bolt_unlinked(const merge_out& o, size_t n_out, const uint8_t*
                                 const uint64_t* pred, uint32_t* flag, hipStream_t st);
 hipError_t launch_bolt_compact(const uint64_t* rounds, const uint32_t* off, size_t n, uint64_t* out, hipStream_t st);
 
+// Unordered candidate columns -> one chain (k_assemble.hip, assemble.hpp). pre: the status byte of a
+// skipped / stale candidate and the live flag (then launch_scan: pos, n + 1 words); cut: the live candidates' keys and
+// input positions in input order. The sort is a stable LSD radix sort of (u64 key, u32 payload) by 8-bit digits:
+// sort_orand ORs / ANDs every key into orand[0] / orand[1] (set to {0, ~0} by the caller), which names the passes
+// whose digit is constant; sort_pass is one pass at bit `shift` from (keys, idx) into (keys_out, idx_out), with cnt and
+// off of 256 x tiles (+ 1) words, digit-major. launch_scan takes 4096^2 counts, so 65536 tiles of SORT_TILE keys, 2^27
+// keys, eight times the 16M rows a column call takes. heads / runs: the rounds' runs of the sorted entries (head -> scan
+// -> run_start per run). class: rep[j] = the sorted entry that entry j repeats, is_rep[j] (then launch_scan: rpos);
+// reps: rep_cand[place in the verifier's columns] = candidate; gather: rows [0, k) of one window of those columns.
+// pick: chosen[run]; select: the live candidates' status bytes and the chosen flags (then launch_scan: opos); emit:
+// the output columns at sig_stride / prev_stride of the input; link: the rows' flags and gap[n_out + 1] (then
+// launch_scan: goff); gaps: the ranges of missing rounds.
+namespace assemble {
+struct cols;
+struct bounds;
+}
+constexpr uint32_t SORT_TILE = 2048;
+struct assemble_verify_cols {
+  uint64_t* rounds;
+  uint8_t* sigs;
+  uint8_t* prevs;
+  uint32_t* prev_lens;
+  uint32_t sig_stride, prev_stride;
+};
+struct assemble_out {
+  uint64_t* rounds;
+  uint8_t* sigs;
+  uint32_t* sig_lens;
+  uint8_t* prevs;  // nullable with prev_lens
+  uint32_t* prev_lens;
+  uint32_t* src;
+  uint8_t* flags;
+};
+hipError_t launch_assemble_pre(const assemble::cols& c, size_t n, const assemble::bounds& b, uint8_t* status, uint32_t* live, hipStream_t st);
+hipError_t launch_assemble_cut(const uint64_t* rounds, size_t n, const uint32_t* pos, uint64_t* keys, uint32_t* idx, hipStream_t st);
+hipError_t launch_sort_orand(const uint64_t* keys, size_t n, uint64_t* orand, hipStream_t st);
+hipError_t launch_sort_pass(const uint64_t* keys, const uint32_t* idx, size_t n, uint32_t shift, uint32_t* cnt, uint32_t* off,
+                            uint32_t* scan_tmp, uint64_t* keys_out, uint32_t* idx_out, hipStream_t st);
+hipError_t launch_assemble_heads(const uint64_t* keys, size_t m, uint32_t* head, hipStream_t st);
+hipError_t launch_assemble_runs(const uint32_t* runs, size_t m, uint32_t* run_start, hipStream_t st);
+hipError_t launch_assemble_class(const assemble::cols& c, const uint32_t* idx, const uint32_t* runs, const uint32_t* run_start, size_t m,
+                                 bool dedupe, uint32_t* rep, uint32_t* is_rep, hipStream_t st);
+hipError_t launch_assemble_reps(const uint32_t* idx, const uint32_t* rpos, size_t m, uint32_t* rep_cand, hipStream_t st);
+hipError_t launch_assemble_gather(const assemble::cols& c, const uint32_t* rep_cand, size_t k, uint32_t want_sig_len,
+                                  const assemble_verify_cols& v, hipStream_t st);
+hipError_t launch_assemble_pick(const assemble::cols& c, const uint32_t* idx, const uint32_t* run_start, size_t n_runs, size_t m,
+                                const uint32_t* rpos, const uint8_t* verdict, uint32_t want_sig_len, uint32_t* chosen, hipStream_t st);
+hipError_t launch_assemble_select(const assemble::cols& c, const uint32_t* idx, const uint32_t* runs, const uint32_t* run_start,
+                                  const uint32_t* rep, const uint32_t* rpos,
+                                  const uint8_t* verdict, const uint32_t* chosen, size_t m, uint32_t want_sig_len, uint8_t* status,
+                                  uint32_t* out_flag, hipStream_t st);
+hipError_t launch_assemble_emit(const assemble::cols& c, const uint32_t* idx, const uint32_t* opos, size_t m, const assemble_out& o,
+                                hipStream_t st);
+hipError_t launch_assemble_link(const assemble::cols& c, const assemble_out& o, size_t n_out, const assemble::bounds& b, const uint64_t* anchor,
+                                bool chained, uint32_t* gap, hipStream_t st);
+hipError_t launch_assemble_gaps(const assemble_out& o, size_t n_out, const assemble::bounds& b, const uint32_t* goff, uint64_t* gap_first,
+                                uint64_t* gap_last, hipStream_t st);
+
 #ifdef DH_COUNT_PRODUCTS
 // counting build: field products executed since the last take, per translation unit (fp_mul28.hpp)
 hipError_t count_take_prep(unsigned long long* v);

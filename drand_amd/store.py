@@ -1724,3 +1724,319 @@ def export_random_data(store, path, scheme=None, pubkey=None, up_to=None, window
         if os.path.exists(tmp):
             os.unlink(tmp)
     return {"records": records, "bytes": nbytes, "faulty": faulty}
+
+
+# ---- one chain from many unordered sources: dh_assemble_device and its host restatement
+
+AS_CHOSEN, AS_DUPLICATE, AS_INVALID = _lib.DH_AS_CHOSEN, _lib.DH_AS_DUPLICATE, _lib.DH_AS_INVALID
+AS_STALE, AS_SKIPPED, AS_CONFLICT = _lib.DH_AS_STALE, _lib.DH_AS_SKIPPED, _lib.DH_AS_CONFLICT
+AS_GAP, AS_LINK = _lib.DH_AS_GAP, _lib.DH_AS_LINK
+AS_COUNTS = ("candidates", "skipped", "stale", "verified", "invalid", "duplicates", "conflicts", "chosen", "missing", "link_breaks")
+
+
+def _contiguous_up_to(rounds, flags, anchor):
+    """Rule 8: the last round of the output rows' longest prefix with neither flag set; the anchor's round (0 without
+    one) when that prefix is empty."""
+    nz = np.flatnonzero(np.asarray(flags))
+    k = int(nz[0]) if len(nz) else len(rounds)
+    return int(rounds[k - 1]) if k else (int(anchor[0]) if anchor is not None else 0)
+
+
+def assemble_host(candidates, scheme, pubkey, anchor=None, up_to=None, verify=None):
+    """The serial definition of dh_assemble_device and the yardstick of assemble_columns: one chain from candidate
+    records in any order. candidates: dicts {"round", "signature", "previous_signature" (chained), "skip" (optional)} in
+    input order. Rules, in order: a candidate with `skip` is SKIPPED; round 0, a round at or below the anchor's or above
+    up_to is STALE; a candidate whose (round, signature[, previous_signature]) an earlier live candidate has is a
+    DUPLICATE with that one's INVALID bit; every other is a representative, verified once (against its OWN
+    previous_signature), INVALID when its signature has another length than the scheme's or does not verify; the first
+    valid representative of a round is CHOSEN, any other one a CONFLICT. The chosen rows ascend by round with flags GAP
+    (not the row before's round + 1) and LINK (chained, consecutive: previous_signature is not that row's signature),
+    the anchor (round, signature) standing before row 0. verify(scheme, pubkey, records) -> [bool] replaces the device
+    verifier (the CPU tests pass the oracle). Returns {"status", "rounds", "src", "flags", "gaps", "counts",
+    "contiguous_up_to"}."""
+    verify = verify or _verify_records
+    a = _anchor_rec(anchor)
+    n = len(candidates)
+
+    def key(c):
+        return (int(c["round"]), bytes(c["signature"]), bytes(c.get("previous_signature") or b"") if scheme.chained else b"")
+
+    status = [0] * n
+    seen, reps = {}, []  # key -> its representative's position; the representatives in input order
+    for i, c in enumerate(candidates):
+        rnd = int(c["round"])
+        if c.get("skip"):
+            status[i] = AS_SKIPPED
+        elif rnd == 0 or (a is not None and rnd <= a["round"]) or (up_to is not None and rnd > int(up_to)):
+            status[i] = AS_STALE
+        elif key(c) in seen:
+            status[i] = AS_DUPLICATE  # its INVALID bit follows below
+        else:
+            seen[key(c)] = i
+            reps.append(i)
+    todo = [i for i in reps if len(candidates[i]["signature"]) == scheme.sig_len]
+    recs = [dict(zip(("round", "signature", "previous_signature"), key(candidates[i]))) for i in todo]
+    valid = dict(zip(todo, verify(scheme, pubkey, recs))) if todo else {}
+    chosen = {}
+    for i in reps:
+        rnd = int(candidates[i]["round"])
+        if not valid.get(i, False):
+            status[i] = AS_INVALID
+        elif rnd in chosen:
+            status[i] = AS_CONFLICT
+        else:
+            chosen[rnd] = i
+            status[i] = AS_CHOSEN
+    for i, c in enumerate(candidates):
+        if status[i] == AS_DUPLICATE and not valid.get(seen[key(c)], False):
+            status[i] |= AS_INVALID
+    rounds = sorted(chosen)
+    src = [chosen[r] for r in rounds]
+    flags, gaps = [], []
+    before = a
+    for r, i in zip(rounds, src):
+        f = 0
+        if before is not None:
+            if r != before["round"] + 1:
+                f = AS_GAP
+                gaps.append((before["round"] + 1, r - 1))
+            elif scheme.chained and bytes(candidates[i].get("previous_signature") or b"") != before["signature"]:
+                f = AS_LINK
+        flags.append(f)
+        before = {"round": r, "signature": bytes(candidates[i]["signature"])}
+    if up_to is not None and before is not None and before["round"] < int(up_to):
+        gaps.append((before["round"] + 1, int(up_to)))
+    st = np.array(status, np.uint8)
+    counts = [n, int(((st & AS_SKIPPED) != 0).sum()), int(((st & AS_STALE) != 0).sum()), len(reps), int(((st & AS_INVALID) != 0).sum()),
+              int(((st & AS_DUPLICATE) != 0).sum()), int(((st & AS_CONFLICT) != 0).sum()), len(rounds),
+              sum(b - a_ + 1 for a_, b in gaps), sum(1 for f in flags if f & AS_LINK)]
+    return {"status": st, "rounds": rounds, "src": src, "flags": flags, "gaps": gaps, "counts": dict(zip(AS_COUNTS, counts)),
+            "contiguous_up_to": _contiguous_up_to(rounds, flags, anchor)}
+
+
+class Assembled:
+    """What assemble_columns returns: the chain's columns on the device (rounds int64 carrying the u64 bit pattern, sigs
+    uint8[m, stride], lens int32, prevs / prev_lens for the chained scheme or None), src int32[m] (output row -> input
+    position), flags uint8[m] (AS_GAP / AS_LINK), and on the host status uint8[n] (the AS_* bits per candidate), gaps
+    [(first, last)], counts {AS_COUNTS} and contiguous_up_to."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def __len__(self):
+        return int(self.rounds.numel())
+
+    def per_source(self, source_ids):
+        """{source: {"candidates", "chosen", "duplicates", "invalid", "stale", "skipped", "conflicts"}} for source_ids, one
+        small non-negative integer per candidate: numpy.bincount over the status."""
+        ids = np.asarray(source_ids).reshape(-1).astype(np.int64)
+        if len(ids) != len(self.status):
+            raise ValueError("%d source ids for %d candidates" % (len(ids), len(self.status)))
+        k = int(ids.max()) + 1 if len(ids) else 0
+        cols = {"candidates": np.bincount(ids, minlength=k)}
+        for name, bit in (("chosen", AS_CHOSEN), ("duplicates", AS_DUPLICATE), ("invalid", AS_INVALID), ("stale", AS_STALE),
+                          ("skipped", AS_SKIPPED), ("conflicts", AS_CONFLICT)):
+            cols[name] = np.bincount(ids, weights=(self.status & bit) != 0, minlength=k).astype(np.int64)
+        return {s: {name: int(v[s]) for name, v in cols.items()} for s in range(k)}
+
+
+def assemble_columns(scheme, pubkey, rounds, sigs, lens, prevs=None, prev_lens=None, skip=None, anchor=None, up_to=None, window=1 << 20,
+                     seed=0, want_prev=True):
+    """dh_assemble_device over torch device tensors (rounds int64[n] carrying the u64 bit pattern, sigs uint8[n, stride],
+    lens int32[n], prevs / prev_lens likewise for the chained scheme, skip uint8[n] or None): candidates in any order,
+    from any number of sources -> an Assembled. The rules are assemble_host's. want_prev=False leaves the chained
+    scheme's previous_signature output columns out."""
+    import torch
+    lib = _lib.load()
+    dev = torch.device("cuda")
+    n = int(rounds.numel())
+    if n > MAX_CALL_ROWS:
+        raise ValueError("%d candidates: at most %d per call" % (n, MAX_CALL_ROWS))
+    chained = bool(scheme.chained)
+    if chained and n and (prevs is None or prev_lens is None):
+        raise ValueError("the chained scheme needs prevs and prev_lens")
+    if not chained:
+        prevs = prev_lens = None
+    cont = lambda t: t.contiguous() if t is not None else None  # noqa: E731
+    rounds, sigs, lens, prevs, prev_lens, skip = cont(rounds), cont(sigs), cont(lens), cont(prevs), cont(prev_lens), cont(skip)
+    stride = int(sigs.shape[1]) if sigs.dim() == 2 else 0
+    pstride = int(prevs.shape[1]) if prevs is not None else 0
+    out_prev = chained and want_prev
+    o_rounds = torch.empty(n, dtype=torch.int64, device=dev)
+    o_sigs = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+    o_lens = torch.empty(n, dtype=torch.int32, device=dev)
+    o_prevs = torch.empty((n, pstride), dtype=torch.uint8, device=dev) if out_prev else None
+    o_prev_lens = torch.empty(n, dtype=torch.int32, device=dev) if out_prev else None
+    o_src = torch.empty(n, dtype=torch.int32, device=dev)
+    o_flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    ptr = lambda t: (t.data_ptr() or None) if t is not None else None  # noqa: E731
+    a = _anchor_rec(anchor)
+    ar = ctypes.c_uint64(a["round"]) if a else None
+    ut = ctypes.c_uint64(int(up_to)) if up_to is not None else None
+    status = np.zeros(n, np.uint8)
+    counts = (ctypes.c_uint64 * 10)()
+    m, ng = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    cap = 1024
+    while True:
+        gf, gl = np.zeros(cap, np.uint64), np.zeros(cap, np.uint64)
+        rc = lib.dh_assemble_device(
+            scheme.id, bytes(pubkey), len(pubkey), ptr(rounds), ptr(sigs), stride, ptr(lens), ptr(prevs), pstride, ptr(prev_lens), ptr(skip), n,
+            ctypes.byref(ar) if a else None, a["signature"] if a else None, len(a["signature"]) if a else 0,
+            ctypes.byref(ut) if ut is not None else None, int(window), int(seed), ptr(o_rounds), ptr(o_sigs), ptr(o_lens), ptr(o_prevs),
+            ptr(o_prev_lens), ptr(o_src), ptr(o_flags), ctypes.byref(m), ctypes.c_void_p(status.ctypes.data),
+            ctypes.c_void_p(gf.ctypes.data), ctypes.c_void_p(gl.ctypes.data), cap, ctypes.byref(ng), counts, None)
+        if rc == _lib.DH_EINVAL and ng.value > cap:  # the dh_archive_deferred convention: the number needed
+            cap = ng.value
+            continue
+        DeviceBoltStore._raise(rc)
+        break
+    k = m.value
+    flags = o_flags[:k]
+    h_rounds, h_flags = o_rounds[:k].cpu().numpy().view(np.uint64), flags.cpu().numpy()
+    return Assembled(rounds=o_rounds[:k], sigs=o_sigs[:k], lens=o_lens[:k], prevs=o_prevs[:k] if out_prev else None,
+                     prev_lens=o_prev_lens[:k] if out_prev else None, src=o_src[:k], flags=flags, status=status,
+                     gaps=[(int(x), int(y)) for x, y in zip(gf[:ng.value], gl[:ng.value])], counts=dict(zip(AS_COUNTS, [int(x) for x in counts])),
+                     contiguous_up_to=_contiguous_up_to(h_rounds, h_flags, anchor))
+
+
+def _u64_to_i64(r):
+    r = int(r)
+    return r - (1 << 64) if r >> 63 else r
+
+
+def _source_columns(src, scheme, stride):
+    """One source of assemble_archives as (rounds, sigs, lens, prevs | None, prev_lens | None, skip) device tensors at
+    `stride`: a DeviceArchive (either kind; its deferred records resolved on the host and patched in, one that does not
+    decode or is blank sets skip), a DeviceBoltStore (its round records), or a tuple of columns (host or device)."""
+    import torch
+    dev = torch.device("cuda")
+    chained = bool(scheme.chained)
+
+    def patch(cols, resolve_row):
+        rounds, sigs, lens, prevs, prev_lens, deferred = cols
+        skip = torch.zeros(len(rounds), dtype=torch.uint8, device=dev)
+        for i in torch.nonzero(deferred).reshape(-1).cpu().tolist():
+            r = resolve_row(i)
+            if not r or len(r["signature"]) > stride or (chained and len(r["previous_signature"]) > stride):
+                skip[i] = 1
+                continue
+            rounds[i] = _u64_to_i64(r["round"])
+            sigs[i, :len(r["signature"])] = torch.frombuffer(bytearray(r["signature"]), dtype=torch.uint8).to(dev)
+            lens[i] = len(r["signature"])
+            if chained and r["previous_signature"]:
+                prevs[i, :len(r["previous_signature"])] = torch.frombuffer(bytearray(r["previous_signature"]), dtype=torch.uint8).to(dev)
+                prev_lens[i] = len(r["previous_signature"])
+        return rounds, sigs, lens, prevs, prev_lens, skip
+
+    if isinstance(src, DeviceArchive):
+        parts = []
+        for at in range(0, len(src), MAX_CALL_ROWS):
+            rounds, sigs, lens, prevs, prev_lens, _r, _rl, deferred = src.beacons_device(at, MAX_CALL_ROWS, sig_stride=stride, prev_stride=stride,
+                                                                                         want_prev=chained, want_rand=False)
+            parts.append(patch((rounds, sigs, lens, prevs, prev_lens, deferred), lambda i, at=at: src.resolve(at + i)))
+        if not parts:
+            parts = [(torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, stride), dtype=torch.uint8, device=dev),
+                      torch.empty(0, dtype=torch.int32, device=dev), torch.empty((0, stride), dtype=torch.uint8, device=dev) if chained else None,
+                      torch.empty(0, dtype=torch.int32, device=dev) if chained else None, torch.empty(0, dtype=torch.uint8, device=dev))]
+        cat = lambda k: torch.cat([p[k] for p in parts]) if parts[0][k] is not None else None  # noqa: E731
+        return tuple(cat(k) for k in range(6))
+    if isinstance(src, DeviceBoltStore):
+        rng = src.rounds_range()
+        if not rng:
+            none = (np.zeros(0, np.uint64), np.zeros((0, stride), np.uint8), np.zeros(0, np.uint32))
+            return _source_columns(none + (none[1:] if chained else ()), scheme, stride)
+        if not src.untrimmed:  # a trimmed store implies its previous signatures: the row before, where it is round - 1
+            rounds, sigs, lens, _missing = src.columns_device(rng[0], rng[1], max(stride, src._stride()))
+            if sigs.shape[1] > stride:  # a value longer than the common stride: a zero row with its true length
+                sigs = torch.where((lens <= stride)[:, None], sigs[:, :stride], torch.zeros_like(sigs[:, :stride])).contiguous()
+            prevs = prev_lens = None
+            if chained:
+                prevs, prev_lens = torch.zeros_like(sigs), torch.zeros_like(lens)
+                if len(rounds) > 1:
+                    follows = (rounds[1:] == rounds[:-1] + 1) & (lens[:-1] <= stride)
+                    prevs[1:][follows] = sigs[:-1][follows]
+                    prev_lens[1:][follows] = lens[:-1][follows]
+            return rounds, sigs, lens, prevs, prev_lens, torch.zeros(len(rounds), dtype=torch.uint8, device=dev)
+        rounds, sigs, lens, prevs, prev_lens, deferred, _missing = src.beacons_device(rng[0], rng[1], sig_stride=stride, prev_stride=stride,
+                                                                                      want_prev=chained)
+        h_rounds = rounds.cpu().numpy().view(np.uint64)
+
+        def resolve(i):
+            try:
+                b = beacon_from_hexjson(src._raw(int(h_rounds[i])))
+            except DECODE_ERRORS:
+                return False
+            return {"round": int(b.round), "signature": bytes(b.signature), "previous_signature": bytes(b.previous_signature or b"")}
+        return patch((rounds, sigs, lens, prevs, prev_lens, deferred), resolve)
+    cols = tuple(src)
+    if len(cols) not in (3, 5):
+        raise ValueError("a column source is (rounds, sigs, lens) or (rounds, sigs, lens, prevs, prev_lens)")
+    rounds, sigs, lens = _device_columns(*cols[:3])
+    prevs = prev_lens = None
+    if chained:
+        if len(cols) != 5:
+            raise ValueError("the chained scheme needs prevs and prev_lens")
+        _r, prevs, prev_lens = _device_columns(rounds, cols[3], cols[4])
+
+    def widen(t):  # to the common stride; a narrower source is zero-padded, a wider one must hold no longer value
+        if t.shape[1] == stride:
+            return t
+        out = torch.zeros((t.shape[0], stride), dtype=torch.uint8, device=dev)
+        w = min(stride, int(t.shape[1]))
+        out[:, :w] = t[:, :w]
+        return out
+    skip = torch.zeros(len(rounds), dtype=torch.uint8, device=dev)
+    for t, l in ((sigs, lens), (prevs, prev_lens)):
+        if t is not None and t.shape[1] > stride and len(l) and int(l.max()) > stride:
+            raise ValueError("a value of %d bytes in a column source: the common stride is %d" % (int(l.max()), stride))
+    return rounds, widen(sigs), lens, widen(prevs) if prevs is not None else None, prev_lens, skip
+
+
+def assemble_archives(sources, scheme, pubkey, anchor=None, up_to=None, window=1 << 20, seed=0, want_prev=True):
+    """One assemble_columns call over any mix of sources: DeviceArchive handles (JSON lines or protobuf records),
+    DeviceBoltStore handles, and (rounds, sigs, lens[, prevs, prev_lens]) column tuples. The columns are concatenated at
+    one stride, roundup4(the scheme's signature length): a decoded value longer than that is an all-zero row with its
+    true length (the device gather's rule) and so invalid. Records the device defers are decoded here and patched into
+    the columns; one that does not decode, or a blank line, sets `skip`. Returns (Assembled, source_ids): source_ids
+    int32[n] names each candidate's source, for Assembled.per_source."""
+    import torch
+    stride = max(4, (scheme.sig_len + 3) & ~3)
+    parts = [_source_columns(s, scheme, stride) for s in sources]
+    ids = np.concatenate([np.full(len(p[0]), k, np.int32) for k, p in enumerate(parts)]) if parts else np.zeros(0, np.int32)
+    dev = torch.device("cuda")
+    if not parts:
+        parts = [(torch.empty(0, dtype=torch.int64, device=dev), torch.empty((0, stride), dtype=torch.uint8, device=dev),
+                  torch.empty(0, dtype=torch.int32, device=dev), None, None, torch.empty(0, dtype=torch.uint8, device=dev))]
+    cat = lambda k: torch.cat([p[k] for p in parts])  # noqa: E731
+    chained = bool(scheme.chained)
+    res = assemble_columns(scheme, pubkey, cat(0), cat(1), cat(2), cat(3) if chained else None, cat(4) if chained else None, cat(5),
+                           anchor=anchor, up_to=up_to, window=window, seed=seed, want_prev=want_prev)
+    return res, ids
+
+
+def _assemble_refusal(res):
+    breaks = [int(r) for r, f in zip(res.rounds.cpu().numpy().view(np.uint64), res.flags.cpu().numpy()) if f & AS_LINK]
+    return "the sources do not support one chain: %d gaps (%s%s), %d link breaks (%s%s)" % (
+        len(res.gaps), ", ".join("%d-%d" % g for g in res.gaps[:8]), ", ..." if len(res.gaps) > 8 else "",
+        len(breaks), ", ".join(map(str, breaks[:8])), ", ..." if len(breaks) > 8 else "")
+
+
+def assemble_to_trimmed_store(sources, path, scheme, pubkey, anchor=None, allow_gaps=False, up_to=None, window=STREAM_WINDOW, seed=0,
+                              page_size=4096):
+    """The chain that `sources` (as assemble_archives takes them) support -> a trimmed store file at `path`: one
+    assemble, then the chosen rows stream from the device into a BoltWriter, `window` rows at a time. A gap or a link
+    break raises ValueError naming the first of them unless allow_gaps; so does an empty chain (NoBeaconStored). With a
+    clean result the file is byte for byte write_trimmed_bolt of the same rows. Returns BoltWriter.finish()'s dict with
+    "assembled": the Assembled and "source_ids"."""
+    res, ids = assemble_archives(sources, scheme, pubkey, anchor=anchor, up_to=up_to, window=window, seed=seed, want_prev=False)
+    if not allow_gaps and (res.gaps or res.counts["link_breaks"] or bool((res.flags != 0).any())):
+        raise ValueError(_assemble_refusal(res))
+    if not len(res):
+        raise NoBeaconStored("the sources hold no valid record")
+    window = max(1, min(int(window), MAX_CALL_ROWS))
+    with BoltWriter(path, page_size) as w:
+        for at in range(0, len(res), window):
+            w.append(res.rounds[at:at + window], res.sigs[at:at + window], res.lens[at:at + window])
+        out = w.finish()
+    return dict(out, assembled=res, source_ids=ids)

@@ -439,4 +439,52 @@ def sync_from_frames(frames, scheme, pubkey, store, up_to, beacon_id="", resync=
     return (False, stored)
 
 
+def sync_from_sources(sources, scheme, pubkey, store, up_to, beacon_id="", window=1 << 20, seed=0):
+    """The sync of a store from many sources at once: what the SyncManager reaches by walking its peers one
+    after another (/root/reference/chain/beacon/sync_manager.go:299-323), from every peer's buffered records in one
+    pass. `sources` is what store.assemble_archives takes: DeviceArchive handles (protobuf packet runs or RandomData
+    archives), DeviceBoltStore handles and column tuples, in any order, overlapping, with holes and bad records. A protobuf
+    source whose first record carries another beacon ID is dropped whole, as tryNode drops such a peer (:385-389). One
+    assemble runs with the store's Last() as the anchor; the rows up to contiguous_up_to are Put through ChainStore with
+    the BeaconAlreadyStored / PutError handling of sync_from_frames. Returns (done, stored rounds, gaps): done = up_to was
+    reached, gaps = the ranges of rounds up to up_to that no source supports with a valid record."""
+    from .store import AS_GAP, AS_LINK, DeviceArchive, _id_bits, assemble_archives
+    stored = []
+    if not isinstance(store, ChainStore):
+        try:
+            store = ChainStore(store, scheme)
+        except NoBeaconStored:
+            return (False, stored, [])  # tryNode: "unable to fetch from store"
+    last = store.last()
+    anchor = (int(last.round), bytes(last.signature))
+    kept = []
+    for s in sources:
+        if isinstance(s, DeviceArchive) and s.kind and len(s):
+            first = s.resolve(0)
+            if first and _id_bits(first, beacon_id):
+                continue
+        kept.append(s)
+    res, _ids = assemble_archives(kept, scheme, pubkey, anchor=anchor, up_to=up_to, window=window, seed=seed)
+    flags = res.flags.cpu().numpy()
+    bad = np.flatnonzero(flags & (AS_GAP | AS_LINK))
+    k = int(bad[0]) if len(bad) else len(flags)
+    rounds = res.rounds[:k].cpu().numpy().view(np.uint64)
+    sigs, lens = res.sigs[:k].cpu().numpy(), res.lens[:k].cpu().numpy()
+    prevs = res.prevs[:k].cpu().numpy() if res.prevs is not None else None
+    prev_lens = res.prev_lens[:k].cpu().numpy() if res.prevs is not None else None
+    for i in range(k):
+        rnd = int(rounds[i])
+        prev = prevs[i, :prev_lens[i]].tobytes() if prevs is not None else b""
+        try:
+            store.put(Beacon(rnd, sigs[i, :lens[i]].tobytes(), prev))
+        except BeaconAlreadyStored:
+            return (rnd == up_to, stored, res.gaps)
+        except PutError:
+            return (False, stored, res.gaps)
+        stored.append(rnd)
+        if rnd == up_to:
+            return (True, stored, res.gaps)
+    return (False, stored, res.gaps)
+
+
 END = _END

@@ -714,6 +714,60 @@ int dh_rand_encode_device(int form, const uint64_t* d_rounds, const uint8_t* d_s
                           uint32_t* d_rec_len_out, size_t* len_out, void* hip_stream);
 
 /*
+ * One chain from many unordered sources. The n candidates are rows of verifier columns in DEVICE
+ * memory, in any order, from any number of sources, the layout dh_archive_beacons_device, dh_store_beacons_device and
+ * dh_store_columns_device write; the call knows no source kind. Rules, in order (store.assemble_host restates them):
+ *   1. a candidate whose d_skip byte (nullable column) is not 0 is SKIPPED;
+ *   2. round 0, a round at or below *anchor_round, or above *up_to (each nullable) is STALE and never verified;
+ *   3. a candidate that repeats an earlier live candidate of its round (the same lengths and bytes of the signature
+ *      and, chained, of the previous_signature) is a DUPLICATE: not verified, it takes the INVALID bit of that one;
+ *   4. every other candidate is a representative, verified once, `window` rows at a time through
+ *      dh_verify_batch_device (the chained scheme against its OWN previous_signature): INVALID when its signature
+ *      length is not dh_sig_len(scheme), when a value is longer than its stride, or when the verifier rejects it;
+ *   5. per round the valid representative lowest in input order is CHOSEN; another valid one with other bytes is a
+ *      CONFLICT (reported, never resolved);
+ *   6. the chosen rows in ascending round order are the output: *m_out whole, zero-padded rows at sig_stride /
+ *      prev_stride (room for n rows; d_prevs_out / d_prev_lens_out nullable together, chained only), d_src_out = the
+ *      input position of each, d_flags_out = DH_AS_GAP when the round is not the row before's + 1, DH_AS_LINK (chained,
+ *      consecutive rounds) when its own previous_signature is not that row's signature; the row before row 0 is the
+ *      anchor when there is one;
+ *   7. the gaps are the maximal ranges of missing rounds from anchor + 1 (without an anchor: from the first chosen
+ *      round) to the last chosen round, or to *up_to when given: gap_first_out / gap_last_out (HOST, gap_cap entries);
+ *      more than gap_cap: DH_EINVAL with *n_gaps_out = the number and everything else written.
+ * Copies are collapsed against the first 16 candidates of their round only (ASSEMBLE_LOOKBACK): a later copy is
+ * verified again, is not a CONFLICT and is marked DUPLICATE when it is valid; the output never depends on it.
+ * DRANDHIP_ASSEMBLE_DEDUPE=0 (read at every call) makes every candidate a representative.
+ * status_out: HOST, n bytes of DH_AS_* bits. counts_out = {candidates, skipped, stale, representatives verified,
+ * invalid, duplicates, conflicts, chosen, missing rounds (saturating), link breaks}. n = 0 is DH_OK; more than 16M
+ * candidates, a stride that is not a positive multiple of 4 up to 1 MiB or a row that is not 4-byte aligned is
+ * DH_EINVAL. Blocking and thread-safe: a call owns its stream and buffers; it waits for hip_stream first. The same
+ * input gives the same output, byte for byte, on every run. dh_profile stages: assemble_sort, assemble_class,
+ * assemble_verify, assemble_select.
+ */
+#define DH_AS_CHOSEN 1
+#define DH_AS_DUPLICATE 2
+#define DH_AS_INVALID 4
+#define DH_AS_STALE 8
+#define DH_AS_SKIPPED 16
+#define DH_AS_CONFLICT 32
+#define DH_AS_GAP 1  /* output-row flags */
+#define DH_AS_LINK 2
+int dh_assemble_device(int scheme, const uint8_t* pk, size_t pk_len, const uint64_t* d_rounds, const uint8_t* d_sigs, size_t sig_stride,
+                       const uint32_t* d_sig_lens, const uint8_t* d_prevs, size_t prev_stride, const uint32_t* d_prev_lens,
+                       const uint8_t* d_skip, size_t n, const uint64_t* anchor_round, const uint8_t* anchor_sig, size_t anchor_sig_len,
+                       const uint64_t* up_to, size_t window, uint64_t seed, uint64_t* d_rounds_out, uint8_t* d_sigs_out,
+                       uint32_t* d_sig_lens_out, uint8_t* d_prevs_out, uint32_t* d_prev_lens_out, uint32_t* d_src_out, uint8_t* d_flags_out,
+                       size_t* m_out, uint8_t* status_out, uint64_t* gap_first_out, uint64_t* gap_last_out, size_t gap_cap,
+                       size_t* n_gaps_out, uint64_t counts_out[10], void* hip_stream);
+
+/*
+ * Test entry (test infrastructure, no product path calls it): the stable sort of dh_assemble_device alone. keys: n u64
+ * keys, perm_out: n positions, both HOST; perm_out[j] = the position of the key that sorts j-th, equal keys in input
+ * order. n = 0 succeeds; more than 16M keys is DH_EINVAL.
+ */
+int dh_sort_rounds_debug(const uint64_t* keys, size_t n, uint32_t* perm_out);
+
+/*
  * Live kernel timing: when enabled, every device stage of the verification path is bracketed by HIP
  * events on the stream it is launched on; dh_profile_read writes a JSON object
  * {"stage": {"count": c, "total_ms": t}, ...} into buf (returns the full length). dh_profile resets.
