@@ -89,6 +89,35 @@ struct dbuf {
   }
 };
 
+struct dbuf_pool {  // a call's own buffers and stream: nothing is shared between calls
+  std::vector<dbuf*> bufs;
+  hipStream_t st = nullptr;  // stays null in a call that runs on its caller's stream
+  ~dbuf_pool() {
+    for (dbuf* b : bufs) b->release();
+    if (st) (void)hipStreamDestroy(st);
+  }
+};
+
+// Environment knobs. Each helper reads the variable when it is called: an accessor that keeps the result in a
+// `static const` reads its knob once per process, one that returns the call's value reads it at every call (the knobs
+// that tests set between calls).
+// A switch: a value starting with '0' turns a default-on knob off, one starting with '1' turns a default-off knob on.
+bool env_on(const char* name, bool def) {
+  const char* e = getenv(name);
+  return e && e[0] == (def ? '0' : '1') ? !def : def;
+}
+// A number as atol reads it; `unset` when the variable is not set.
+long env_long(const char* name, long unset) {
+  const char* e = getenv(name);
+  return e ? atol(e) : unset;
+}
+// A size as atoll reads it when that is at least `min` (>= 0); otherwise, and when the variable is not set, `def`.
+size_t env_size(const char* name, size_t def, long long min) {
+  const char* e = getenv(name);
+  const long long v = e ? atoll(e) : -1;
+  return v >= min ? (size_t)v : def;
+}
+
 struct worker {
   hipStream_t stream = nullptr;
   // high-priority stream for a batch's latency-bound tail (MSM, pairing checks, bisection): its small kernels
@@ -198,8 +227,7 @@ struct context {
   // streams until the runtime runs out of hardware-queue resources (r03: 16 node batches in flight, each holding two
   // workers, aborted HSA queues with HSA_STATUS_ERROR_OUT_OF_RESOURCES); DRANDHIP_MAX_WORKERS overrides
   size_t max_workers = [] {
-    const char* e = getenv("DRANDHIP_MAX_WORKERS");
-    const long v = e ? atol(e) : 0;
+    const long v = env_long("DRANDHIP_MAX_WORKERS", 0);
     return (size_t)(v >= 1 && v <= 256 ? v : 24);
   }();
   std::vector<worker*> pool;     // idle or leased workers
@@ -239,8 +267,7 @@ int ensure_init_locked(uint32_t mask) {
 // deadlock. DRANDHIP_LEASE_TIMEOUT_MS overrides (default 30 s).
 static std::chrono::milliseconds node_held_timeout() {
   static const long v = [] {
-    const char* e = getenv("DRANDHIP_LEASE_TIMEOUT_MS");
-    const long x = e ? atol(e) : 0;
+    const long x = env_long("DRANDHIP_LEASE_TIMEOUT_MS", 0);
     return x > 0 ? x : 30000L;
   }();
   return std::chrono::milliseconds(v);
@@ -680,10 +707,7 @@ struct timed_launches {
 // Pairing checks: the lane-parallel program (k_vm.hip) unless DRANDHIP_LANE_PAIRING=1 selects the one-lane
 // tower code (k_check.hip), kept as the independent second implementation the parity tests compare against.
 static bool lane_pairing() {
-  static const bool v = [] {
-    const char* e = getenv("DRANDHIP_LANE_PAIRING");
-    return e && e[0] == '1';
-  }();
+  static const bool v = env_on("DRANDHIP_LANE_PAIRING", false);
   return v;
 }
 
@@ -692,30 +716,21 @@ static bool lane_pairing() {
 // clearing's doublings spread over the lanes) instead of on one lane before it; DRANDHIP_NP2C=0 turns it off. Above
 // it the one-lane clearing wins: every group's lane runs in parallel, the NP2C workgroups queue for the CUs.
 static size_t np2c_max_groups() {
-  static const size_t v = [] {
-    const char* e = getenv("DRANDHIP_NP2C");
-    return e && e[0] == '0' ? (size_t)0 : (size_t)4096;
-  }();
+  static const size_t v = env_on("DRANDHIP_NP2C", true) ? 4096 : 0;
   return v;
 }
 
 // G2-signature leaves (per-round checks: bisection leaves and the small-batch path) likewise, up to this many per
 // launch; DRANDHIP_NP2C_LEAVES overrides (0: every leaf clears its hash point on one lane first)
 static size_t np2c_max_leaves() {
-  static const size_t v = [] {
-    const char* e = getenv("DRANDHIP_NP2C_LEAVES");
-    return e ? (size_t)atol(e) : (size_t)4096;
-  }();
+  static const size_t v = (size_t)env_long("DRANDHIP_NP2C_LEAVES", 4096);
   return v;
 }
 
 // G1-signature checks with [h_eff] pk at hand take their G1 sides in Jacobian form (NP2J: no prep kernel, no
 // inversion before the program); DRANDHIP_G1_JAC=0 keeps the affine prep (k_vm_prep_groups / _leaves) for A/B runs
 static bool g1_jac() {
-  static const bool v = [] {
-    const char* e = getenv("DRANDHIP_G1_JAC");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_on("DRANDHIP_G1_JAC", true);
   return v;
 }
 
@@ -830,19 +845,13 @@ static size_t next_group_size(size_t gsize, size_t ngroups, size_t nfail, size_t
 }
 
 static bool prep_sync() {
-  static const bool v = [] {
-    const char* e = getenv("DRANDHIP_PREP_SYNC");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_on("DRANDHIP_PREP_SYNC", true);
   return v;
 }
 
 // DRANDHIP_SKIP_LEVEL0=0 keeps level 0 on dense-fault workers (comparison runs)
 static bool skip_level0() {
-  static const bool v = [] {
-    const char* e = getenv("DRANDHIP_SKIP_LEVEL0");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_on("DRANDHIP_SKIP_LEVEL0", true);
   return v;
 }
 
@@ -875,18 +884,11 @@ struct prep_gate {
 // below ~100k rounds the fused kernel's per-round test costs one call less than that (4,096 rounds: 7.36 ms fused,
 // 7.72 batched; 65,536: 8.94 / 9.27; 131,072: 11.10 / 10.96; 1M: 45.7 / 34.2).
 static bool subgroup_batch_on() {
-  static const bool v = [] {
-    const char* e = getenv("DRANDHIP_SUBGROUP_BATCH");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_on("DRANDHIP_SUBGROUP_BATCH", true);
   return v;
 }
 static size_t sub_batch_min() {
-  static const size_t v = [] {
-    const char* e = getenv("DRANDHIP_SUB_BATCH_MIN");
-    const long long d = e ? atoll(e) : 0;
-    return (size_t)(d >= 1 ? d : 131072);
-  }();
+  static const size_t v = env_size("DRANDHIP_SUB_BATCH_MIN", 131072, 1);
   return v;
 }
 // The same for G2 signatures: an eligible batch runs its MSMs on two 63-bit psi halves instead of four
@@ -897,11 +899,7 @@ static size_t sub_batch_min() {
 // the latency path (262,144 rounds: 30.5 ms fused, 30.8 batched; 393,216: 39.6-40.2 / 37.9; 1M: 84.4-84.9 / 69.8-70.0).
 constexpr size_t SUB_BATCH_MIN_G2_DEFAULT = 393216;
 static size_t sub_batch_min_g2() {
-  static const size_t v = [] {
-    const char* e = getenv("DRANDHIP_SUB_BATCH_MIN_G2");
-    const long long d = e ? atoll(e) : 0;
-    return (size_t)(d >= 1 ? d : SUB_BATCH_MIN_G2_DEFAULT);
-  }();
+  static const size_t v = env_size("DRANDHIP_SUB_BATCH_MIN_G2", SUB_BATCH_MIN_G2_DEFAULT, 1);
   return v;
 }
 // A batch whose fallback flagged more than one round in 2000 (a replay over a store with corrupted signatures: the
@@ -910,8 +908,7 @@ static size_t sub_batch_min_g2() {
 // path (profiles/r07/faulted_quicknet_262144_no_backoff.jsonl); sparse faults (the odd bad round) do not start it.
 static int sub_backoff() {
   static const int v = [] {
-    const char* e = getenv("DRANDHIP_SUB_BACKOFF");
-    const long d = e ? atol(e) : -1;
+    const long d = env_long("DRANDHIP_SUB_BACKOFF", -1);
     return (int)(d >= 0 && d <= 1 << 20 ? d : 15);
   }();
   return v;
@@ -921,10 +918,7 @@ static int sub_backoff() {
 // point's inversion riding on the decode's square-root chain (k_prep.hip round_g1_ride).
 // DRANDHIP_G1_RIDE=0 launches the two previous kernels (comparison runs).
 static bool g1_ride_on() {
-  static const bool v = [] {
-    const char* e = getenv("DRANDHIP_G1_RIDE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_on("DRANDHIP_G1_RIDE", true);
   return v;
 }
 
@@ -934,10 +928,7 @@ static bool g1_ride_on() {
 // that level 0 does not end falls back to the isogeny per round and the usual arrays (points beside their images) before level 1.
 // DRANDHIP_G1_ISO_LATE=0 keeps the isogeny in the per-round kernel (comparison runs).
 static bool g1_iso_late_on() {
-  static const bool v = [] {
-    const char* e = getenv("DRANDHIP_G1_ISO_LATE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_on("DRANDHIP_G1_ISO_LATE", true);
   return v;
 }
 
@@ -946,10 +937,7 @@ static bool g1_iso_late_on() {
 // 2^-62 (the batched subgroup test's 2^-63 and the check's 2^-63); a batch that level 0 does not end is re-checked by
 // the fallback and the bisection on r_i = a_i + mu b_i, as before. DRANDHIP_G1_RLC_HALF=0 keeps both halves at level 0.
 static bool g1_rlc_half_on() {
-  static const bool v = [] {
-    const char* e = getenv("DRANDHIP_G1_RLC_HALF");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_on("DRANDHIP_G1_RLC_HALF", true);
   return v;
 }
 // the shape of the calling thread's last level-0 MSM (dh_msm_level0_shape_debug)
@@ -1283,10 +1271,7 @@ int verify_core(worker* w, int scheme, const uint8_t* pk, size_t pk_len, const u
 // verdicts by construction). A round's check is one wave per round, so up to a few hundred rounds cost what one does;
 // larger batches amortise one group check over an MSM instead (verify_core). DRANDHIP_SMALL_N overrides (0: off).
 static size_t small_batch_max() {
-  static const size_t v = [] {
-    const char* e = getenv("DRANDHIP_SMALL_N");
-    return e ? (size_t)atol(e) : (size_t)64;
-  }();
+  static const size_t v = (size_t)env_long("DRANDHIP_SMALL_N", 64);
   return v;
 }
 
@@ -2158,8 +2143,7 @@ int run_split(size_t n, F&& fn, uint64_t seed) {
 
 }  // namespace
 
-static void stores_shutdown();  // store handles, below
-static void archives_shutdown();  // archive handles, below
+static void handles_shutdown();  // store, writer and archive handles, below
 
 extern "C" {
 
@@ -2169,8 +2153,7 @@ int dh_init(uint32_t device_mask) {
 }
 
 void dh_shutdown(void) {
-  stores_shutdown();  // store handles (dh_store_open_bolt) are invalidated; one inside a call when that call ends
-  archives_shutdown();  // and archive handles (dh_archive_open_ndjson)
+  handles_shutdown();  // store, writer and archive handles are invalidated; one inside a call when that call ends
   // idle workers are freed now; a worker leased by a call still running on another thread is retired and freed
   // when that call returns, so the call never touches freed memory
   std::lock_guard<std::mutex> lk(g_ctx.mu);
@@ -2366,10 +2349,7 @@ int dh_partial_bytes(int scheme) {
 // kernels cost the other batches' dispatch (the local path's host wait before queueing its tail is the same fix).
 // DRANDHIP_NODE_ONE_STREAM=0 restores the tail-stream handoff (comparison runs).
 static bool node_one_stream() {
-  static const bool v = [] {
-    const char* e = getenv("DRANDHIP_NODE_ONE_STREAM");
-    return !(e && e[0] == '0');
-  }();
+  static const bool v = env_on("DRANDHIP_NODE_ONE_STREAM", true);
   return v;
 }
 static hipStream_t batch_stream(worker* w) { return node_one_stream() ? w->stream : w->tail; }
@@ -2668,6 +2648,36 @@ int dh_verify_partials_batch(int scheme, const uint8_t* commits, int t, int n_no
                       L.w->stream, ok_out);
 }
 
+// The items of dh_bls_verify_batch and dh_schnorr_verify_batch: the refusals the two calls share (sl: the scheme's
+// signature length, n_limit: the caller's bound on n), each item's key index, its message offset from msg_off[0], and
+// the number of distinct keys the items name.
+struct keyed_items {
+  std::vector<uint32_t> kidx, off;
+  size_t keys_used = 0;
+  int check(const uint8_t* keys, size_t n_keys, const uint32_t* key_idx, const uint8_t* msgs, const uint32_t* msg_off, const uint8_t* sigs,
+            size_t sig_stride, size_t sl, size_t n, size_t n_limit, const uint8_t* verdict_out) {
+    if (n_keys && !keys) return fail(DH_EINVAL, "null key table");
+    if (!key_idx && n_keys != n) return fail(DH_EINVAL, "key_idx is null: one key per item, yet %zu keys for %zu items", n_keys, n);
+    if (n && !n_keys) return fail(DH_EINVAL, "%zu items and no keys", n);
+    if (n && (!msg_off || !sigs || !verdict_out)) return fail(DH_EINVAL, "null argument");
+    if (sig_stride < sl || sig_stride % 4) return fail(DH_EINVAL, "bad signature stride %zu", sig_stride);
+    if (n >= n_limit || n_keys > ((size_t)1 << 24)) return fail(DH_EINVAL, "batch too large");
+    kidx.assign(n, 0);
+    off.assign(n + 1, 0);
+    std::vector<uint8_t> used(n_keys, 0);
+    for (size_t i = 0; i < n; i++) {
+      if (msg_off[i + 1] < msg_off[i]) return fail(DH_EINVAL, "msg_off must be non-decreasing");
+      const uint32_t k = key_idx ? key_idx[i] : (uint32_t)i;
+      if (k >= n_keys) return fail(DH_EINVAL, "item %zu: key index %u outside the table of %zu keys", i, k, n_keys);
+      kidx[i] = k;
+      off[i + 1] = msg_off[i + 1] - msg_off[0];
+      if (!used[k]) used[k] = 1, keys_used++;
+    }
+    if (off[n] && !msgs) return fail(DH_EINVAL, "null messages");
+    return DH_OK;
+  }
+};
+
 int dh_bls_verify_batch(int scheme, const uint8_t* keys, size_t n_keys, const uint32_t* key_idx, const uint8_t* msgs,
                         const uint32_t* msg_off, const uint8_t* sigs, size_t sig_stride, size_t n, uint8_t* verdict_out,
                         uint8_t* key_ok_out, uint64_t seed, uint64_t stats_out[4]) {
@@ -2675,31 +2685,14 @@ int dh_bls_verify_batch(int scheme, const uint8_t* keys, size_t n_keys, const ui
   const bool g2 = sig_on_g2(scheme);
   const size_t sl = g2 ? 96 : 48;
   if (stats_out) memset(stats_out, 0, 4 * sizeof(uint64_t));
-  if (n_keys && !keys) return fail(DH_EINVAL, "null key table");
-  if (!key_idx && n_keys != n) return fail(DH_EINVAL, "key_idx is null: one key per item, yet %zu keys for %zu items", n_keys, n);
-  if (n && !n_keys) return fail(DH_EINVAL, "%zu items and no keys", n);
-  if (n && (!msg_off || !sigs || !verdict_out)) return fail(DH_EINVAL, "null argument");
-  if (sig_stride < sl || sig_stride % 4) return fail(DH_EINVAL, "bad signature stride %zu", sig_stride);
   // entries of the MSM's sorted list keep a sign bit and address parts * n points; the key table feeds int-sized kernels
-  if (n >= ((size_t)1 << 31) / (g2 ? 4 : 2) || n_keys > ((size_t)1 << 24)) return fail(DH_EINVAL, "batch too large");
-  std::vector<uint32_t> kidx(n), off(n + 1, 0);
-  std::vector<uint8_t> used(n_keys, 0);
-  size_t keys_used = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (msg_off[i + 1] < msg_off[i]) return fail(DH_EINVAL, "msg_off must be non-decreasing");
-    const uint32_t k = key_idx ? key_idx[i] : (uint32_t)i;
-    if (k >= n_keys) return fail(DH_EINVAL, "item %zu: key index %u outside the table of %zu keys", i, k, n_keys);
-    kidx[i] = k;
-    off[i + 1] = msg_off[i + 1] - msg_off[0];
-    if (!used[k]) used[k] = 1, keys_used++;
-  }
-  if (off[n] && !msgs) return fail(DH_EINVAL, "null messages");
-  if (n == 0) return DH_OK;
+  keyed_items it;
+  int rc = it.check(keys, n_keys, key_idx, msgs, msg_off, sigs, sig_stride, sl, n, ((size_t)1 << 31) / (g2 ? 4 : 2), verdict_out);
+  if (rc || n == 0) return rc;
   lease L;
   if (L.rc) return L.rc;
-  int rc = set_device_and_stream(L.w);
-  if (rc) return rc;
-  rc = auth_core(L.w, scheme, keys, n_keys, kidx.data(), keys_used, msgs ? msgs + msg_off[0] : nullptr, off.data(), sigs, sig_stride,
+  if ((rc = set_device_and_stream(L.w))) return rc;
+  rc = auth_core(L.w, scheme, keys, n_keys, it.kidx.data(), it.keys_used, msgs ? msgs + msg_off[0] : nullptr, it.off.data(), sigs, sig_stride,
                  n, verdict_out, key_ok_out, seed, stats_out, L.w->stream);
   if (rc) (void)hipStreamSynchronize(L.w->stream);  // nothing of this call stays queued on the worker
   return rc;
@@ -2715,27 +2708,13 @@ int dh_schnorr_verify_batch(int scheme, const uint8_t* keys, size_t n_keys, cons
                             uint8_t* key_ok_out) {
   if (scheme < 0 || scheme > 3) return fail(DH_EINVAL, "unknown scheme %d", scheme);
   const size_t sl = (size_t)dh_schnorr_sig_len(scheme);
-  if (n_keys && !keys) return fail(DH_EINVAL, "null key table");
-  if (!key_idx && n_keys != n) return fail(DH_EINVAL, "key_idx is null: one key per item, yet %zu keys for %zu items", n_keys, n);
-  if (n && !n_keys) return fail(DH_EINVAL, "%zu items and no keys", n);
-  if (n && (!msg_off || !sigs || !verdict_out)) return fail(DH_EINVAL, "null argument");
-  if (sig_stride < sl || sig_stride % 4) return fail(DH_EINVAL, "bad signature stride %zu", sig_stride);
-  if (n >= ((size_t)1 << 31) || n_keys > ((size_t)1 << 24)) return fail(DH_EINVAL, "batch too large");
-  std::vector<uint32_t> kidx(n), off(n + 1, 0);
-  for (size_t i = 0; i < n; i++) {
-    if (msg_off[i + 1] < msg_off[i]) return fail(DH_EINVAL, "msg_off must be non-decreasing");
-    const uint32_t k = key_idx ? key_idx[i] : (uint32_t)i;
-    if (k >= n_keys) return fail(DH_EINVAL, "item %zu: key index %u outside the table of %zu keys", i, k, n_keys);
-    kidx[i] = k;
-    off[i + 1] = msg_off[i + 1] - msg_off[0];
-  }
-  if (off[n] && !msgs) return fail(DH_EINVAL, "null messages");
-  if (n == 0) return DH_OK;
+  keyed_items it;
+  int rc = it.check(keys, n_keys, key_idx, msgs, msg_off, sigs, sig_stride, sl, n, (size_t)1 << 31, verdict_out);
+  if (rc || n == 0) return rc;
   lease L;
   if (L.rc) return L.rc;
-  int rc = set_device_and_stream(L.w);
-  if (rc) return rc;
-  rc = schnorr_core(L.w, scheme, keys, n_keys, kidx.data(), msgs ? msgs + msg_off[0] : nullptr, off.data(), sigs, sig_stride, n,
+  if ((rc = set_device_and_stream(L.w))) return rc;
+  rc = schnorr_core(L.w, scheme, keys, n_keys, it.kidx.data(), msgs ? msgs + msg_off[0] : nullptr, it.off.data(), sigs, sig_stride, n,
                     verdict_out, key_ok_out, L.w->stream);
   if (rc) (void)hipStreamSynchronize(L.w->stream);  // nothing of this call stays queued on the worker
   return rc;
@@ -2857,8 +2836,10 @@ static bool fp_bytes_canonical(const uint8_t* b) {
   return memcmp(b, P, 48) < 0;
 }
 
-int dh_g1_round_prep_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uint8_t* status_out, uint8_t* sig_out,
-                           uint8_t* hash_out) {
+// the fused per-round G1 kernel on given field elements; late: the form that leaves the isogeny to the MSM (28-bit
+// columns beside the points)
+static int g1_round_prep_debug(bool late, const uint8_t* us, const uint8_t* sigs, size_t n, uint8_t* status_out, uint8_t* sig_out,
+                               uint8_t* hash_out) {
   if (!us || !sigs || !status_out || !sig_out || !hash_out) return fail(DH_EINVAL, "null argument");
   if (n == 0) return DH_OK;
   for (size_t i = 0; i < 2 * n; i++)
@@ -2874,12 +2855,21 @@ int dh_g1_round_prep_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uin
   HIP_TRY(w->status.ensure(n));
   HIP_TRY(w->sig_aff.ensure(n * JAC_WORDS_G1 * 2 / 3 * 4));
   HIP_TRY(w->q_pts.ensure(n * JAC_WORDS_G1 * 4));
+  if (late) {
+    HIP_TRY(w->s28.ensure(n * 32 * 4));
+    HIP_TRY(w->q28.ensure(n * 32 * 4));
+  }
   HIP_TRY(w->out_rand.ensure(n * 192));
   HIP_TRY(hipMemcpyAsync(w->in_prevs.p, us, n * 96, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(w->in_sigs.p, sigs, n * 48, hipMemcpyHostToDevice, st));
   uint8_t* out = w->out_rand.as<uint8_t>();
-  HIP_TRY(dh::launch_round_g1_ride_debug(w->in_prevs.as<uint8_t>(), w->in_sigs.as<uint8_t>(), n, w->status.as<uint8_t>(),
-                                         w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(), out, out + n * 96, st));
+  if (late)
+    HIP_TRY(dh::launch_round_g1_ride_late_debug(w->in_prevs.as<uint8_t>(), w->in_sigs.as<uint8_t>(), n, w->status.as<uint8_t>(),
+                                                w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(), w->s28.as<uint32_t>(),
+                                                w->q28.as<uint32_t>(), out, out + n * 96, st));
+  else
+    HIP_TRY(dh::launch_round_g1_ride_debug(w->in_prevs.as<uint8_t>(), w->in_sigs.as<uint8_t>(), n, w->status.as<uint8_t>(),
+                                           w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(), out, out + n * 96, st));
   HIP_TRY(hipMemcpyAsync(status_out, w->status.p, n, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(sig_out, out, n * 96, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipMemcpyAsync(hash_out, out + n * 96, n * 96, hipMemcpyDeviceToHost, st));
@@ -2887,37 +2877,14 @@ int dh_g1_round_prep_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uin
   return DH_OK;
 }
 
+int dh_g1_round_prep_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uint8_t* status_out, uint8_t* sig_out,
+                           uint8_t* hash_out) {
+  return g1_round_prep_debug(false, us, sigs, n, status_out, sig_out, hash_out);
+}
+
 int dh_g1_round_prep_late_debug(const uint8_t* us, const uint8_t* sigs, size_t n, uint8_t* status_out, uint8_t* sig_out,
                                 uint8_t* hash_out) {
-  if (!us || !sigs || !status_out || !sig_out || !hash_out) return fail(DH_EINVAL, "null argument");
-  if (n == 0) return DH_OK;
-  for (size_t i = 0; i < 2 * n; i++)
-    if (!fp_bytes_canonical(us + 48 * i)) return fail(DH_EINVAL, "field element %zu is not below p", i);
-  lease L;
-  if (L.rc) return L.rc;
-  worker* w = L.w;
-  int rc = set_device_and_stream(w);
-  if (rc) return rc;
-  hipStream_t st = w->stream;
-  HIP_TRY(w->in_prevs.ensure(n * 96));
-  HIP_TRY(w->in_sigs.ensure(n * 48));
-  HIP_TRY(w->status.ensure(n));
-  HIP_TRY(w->sig_aff.ensure(n * JAC_WORDS_G1 * 2 / 3 * 4));
-  HIP_TRY(w->q_pts.ensure(n * JAC_WORDS_G1 * 4));
-  HIP_TRY(w->s28.ensure(n * 32 * 4));
-  HIP_TRY(w->q28.ensure(n * 32 * 4));
-  HIP_TRY(w->out_rand.ensure(n * 192));
-  HIP_TRY(hipMemcpyAsync(w->in_prevs.p, us, n * 96, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemcpyAsync(w->in_sigs.p, sigs, n * 48, hipMemcpyHostToDevice, st));
-  uint8_t* out = w->out_rand.as<uint8_t>();
-  HIP_TRY(dh::launch_round_g1_ride_late_debug(w->in_prevs.as<uint8_t>(), w->in_sigs.as<uint8_t>(), n, w->status.as<uint8_t>(),
-                                              w->sig_aff.as<uint32_t>(), w->q_pts.as<uint32_t>(), w->s28.as<uint32_t>(),
-                                              w->q28.as<uint32_t>(), out, out + n * 96, st));
-  HIP_TRY(hipMemcpyAsync(status_out, w->status.p, n, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(sig_out, out, n * 96, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(hash_out, out + n * 96, n * 96, hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  return DH_OK;
+  return g1_round_prep_debug(true, us, sigs, n, status_out, sig_out, hash_out);
 }
 
 int dh_field_ops_debug(const uint32_t* ops, const uint32_t* in, size_t in_words, size_t n, uint32_t* out, size_t out_words) {
@@ -2983,10 +2950,8 @@ int dh_public_key(int scheme, const uint8_t* sk32, uint8_t* key_out) {
 // loop over it (chain/beacon/sync_manager.go:170-235). The file image is uploaded once per open store; a window's
 // columns are cut from it by k_bolt.hip in the layout dh_verify_batch_device takes, previous signatures included.
 
-static size_t store_max_bytes() {
-  const char* e = getenv("DRANDHIP_STORE_MAX_BYTES");
-  const long long v = e ? atoll(e) : 0;
-  return v > 0 ? (size_t)v : (size_t)16 << 30;
+static size_t store_max_bytes() {  // read at every call
+  return env_size("DRANDHIP_STORE_MAX_BYTES", (size_t)16 << 30, 1);
 }
 
 struct prof_wall {  // host wall time of one store stage (each ends in a stream wait), recorded when profiling is on
@@ -3053,10 +3018,72 @@ struct write_ws {
   }
 };
 
-struct dh_store {
+// What dh_store, dh_bolt_writer and dh_archive share: locking, and their lifetime across dh_shutdown
+struct dh_handle {
   std::mutex mu;                    // calls on one handle are serialised
   std::atomic<bool> retire{false};  // dh_shutdown ran while a call held the handle: that call (or the next) releases
-  bool dead = false;                // device memory released by dh_shutdown: every call fails, dh_store_close frees
+  bool dead = false;                // device memory released by dh_shutdown: every call fails, dh_*_close frees
+  hipStream_t st = nullptr;
+  virtual ~dh_handle() = default;
+  virtual void release_buffers() = 0;
+  void release() {
+    release_buffers();
+    if (st) (void)hipStreamDestroy(st);
+    st = nullptr;
+    dead = true;
+  }
+};
+static std::mutex g_stores_mu;
+static std::vector<dh_handle*> g_handles;  // every open store, writer and archive, under g_stores_mu
+
+// dh_shutdown: idle handles lose their device memory now, a handle inside a call when that call ends
+static void handles_shutdown() {
+  std::lock_guard<std::mutex> lk(g_stores_mu);
+  for (dh_handle* h : g_handles) {
+    if (h->mu.try_lock()) {
+      h->release();
+      h->mu.unlock();
+    } else {
+      h->retire = true;
+    }
+  }
+}
+
+static void handle_register(dh_handle* h) {
+  std::lock_guard<std::mutex> lk(g_stores_mu);
+  g_handles.push_back(h);
+}
+
+// entered with h->mu held; what / close_fn: the handle's word and its close function in the refusal
+static int handle_enter(dh_handle* h, const char* what, const char* close_fn) {
+  if (h->retire.exchange(false)) h->release();
+  if (h->dead) return fail(DH_EINVAL, "%s handle invalidated by dh_shutdown (%s it and open again)", what, close_fn);
+  HIP_TRY(hipSetDevice(g_ctx.device));
+  return DH_OK;
+}
+struct handle_guard {
+  dh_handle* h;
+  explicit handle_guard(dh_handle* x) : h(x) { h->mu.lock(); }
+  ~handle_guard() {
+    if (h->retire.exchange(false)) h->release();
+    h->mu.unlock();
+  }
+};
+
+static void handle_close(dh_handle* h) {
+  if (!h) return;
+  {
+    std::lock_guard<std::mutex> lk(g_stores_mu);
+    g_handles.erase(std::remove(g_handles.begin(), g_handles.end(), h), g_handles.end());
+  }
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->dead && hipSetDevice(g_ctx.device) == hipSuccess) h->release();
+  }
+  delete h;
+}
+
+struct dh_store : dh_handle {
   size_t len = 0;
   uint32_t page_size = 0;
   uint64_t stat[6] = {0, 0, 0, 0, 0, 0};
@@ -3065,76 +3092,25 @@ struct dh_store {
   std::vector<dh::bolt::leaf_json> jinfo;  // untrimmed: the hexjson scan's table
   std::vector<dh::bolt::leaf_info> info;  // the scan's table, one record per leaf in key order
   std::vector<uint32_t> rleaf;            // the leaves that hold rounds (ascending first / last): the search index
-  hipStream_t st = nullptr;
   dbuf d_file, d_leaves, d_info, err, cnt, base, scan_tmp, rounds, rows, lens, miss_prev, gap, moff, missing, verdict, bad;
   dbuf d_jinfo, prevs, prev_lens, defer;  // untrimmed: rows / lens above hold the decoded Signature column
   std::vector<uint8_t> h_defer;
   std::vector<uint8_t> h_bad;
   std::vector<uint64_t> h_rounds, h_missing;
   write_ws wws;  // dh_store_save_trimmed
-  void release() {
+  void release_buffers() override {
     wws.release();
     for (dbuf* b : {&d_file, &d_leaves, &d_info, &err, &cnt, &base, &scan_tmp, &rounds, &rows, &lens, &miss_prev, &gap, &moff,
                     &missing, &verdict, &bad, &d_jinfo, &prevs, &prev_lens, &defer})
       b->release();
-    if (st) (void)hipStreamDestroy(st);
-    st = nullptr;
-    dead = true;
   }
 };
-struct dh_bolt_writer {  // locking and lifetime as dh_store
-  std::mutex mu;
-  std::atomic<bool> retire{false};
-  bool dead = false;
-  hipStream_t st = nullptr;
+struct dh_bolt_writer : dh_handle {
   bw_state bw;
-  void release() {
-    bw.release();
-    if (st) (void)hipStreamDestroy(st);
-    st = nullptr;
-    dead = true;
-  }
+  void release_buffers() override { bw.release(); }
 };
-static std::mutex g_stores_mu;
-static std::vector<dh_store*> g_stores;
-static std::vector<dh_bolt_writer*> g_writers;  // under g_stores_mu
-
-// dh_shutdown: idle handles lose their device memory now, a handle inside a call when that call ends
-static void stores_shutdown() {
-  std::lock_guard<std::mutex> lk(g_stores_mu);
-  for (dh_store* s : g_stores) {
-    if (s->mu.try_lock()) {
-      s->release();
-      s->mu.unlock();
-    } else {
-      s->retire = true;
-    }
-  }
-  for (dh_bolt_writer* w : g_writers) {
-    if (w->mu.try_lock()) {
-      w->release();
-      w->mu.unlock();
-    } else {
-      w->retire = true;
-    }
-  }
-}
-
-// entered with s->mu held
-static int store_enter(dh_store* s) {
-  if (s->retire.exchange(false)) s->release();
-  if (s->dead) return fail(DH_EINVAL, "store handle invalidated by dh_shutdown (dh_store_close it and open again)");
-  HIP_TRY(hipSetDevice(g_ctx.device));
-  return DH_OK;
-}
-struct store_guard {
-  dh_store* s;
-  explicit store_guard(dh_store* x) : s(x) { s->mu.lock(); }
-  ~store_guard() {
-    if (s->retire.exchange(false)) s->release();
-    s->mu.unlock();
-  }
-};
+static int store_enter(dh_store* s) { return handle_enter(s, "store", "dh_store_close"); }
+static int writer_enter(dh_bolt_writer* w) { return handle_enter(w, "writer", "dh_bolt_writer_close"); }
 
 static int bolt_index(const uint8_t* file, size_t len, dh::bolt::meta* m, std::vector<dh::bolt::leaf_ref>* leaves) {
   using namespace dh::bolt;
@@ -3327,9 +3303,37 @@ static uint32_t window_longest_json(const dh_store* s, size_t lo, size_t nw) {
   return m;
 }
 
-static int store_check_past_json(dh_store* s, int scheme, const uint8_t* pk, size_t pk_len, uint64_t up_to, size_t window,
-                                 uint64_t seed, uint64_t* faulty_out, size_t cap, size_t* n_faulty_out,
-                                 void (*cb)(uint64_t round, uint64_t up_to, void* arg), void* cb_arg);
+// store.Last() of a trimmed store: the largest round; the chained Get also needs the record before it
+// (trimmed.go:156-193)
+static int store_last_trimmed(dh_store* s, bool chained, uint64_t last_round) {
+  if (!chained || !last_round) return DH_OK;
+  size_t lo, nw, total;
+  uint32_t longest;
+  int rc = store_window(s, last_round - 1, last_round, &lo, &nw, &total, &longest);
+  if (rc) return rc;
+  if (total != 2) return fail(DH_ENOBEACON, "no beacon stored: round %llu, before the last", (unsigned long long)(last_round - 1));
+  return DH_OK;
+}
+
+// Last() of an untrimmed store fails on an empty bucket only, but Last().Round is the last record's Round field: known
+// here only when the record is canonical
+static int store_last_json(dh_store* s, uint64_t last_round) {
+  if (!s->jstat[0]) return DH_OK;
+  size_t lo, nw, total;
+  uint32_t longest;
+  int rc = store_window(s, last_round, last_round, &lo, &nw, &total, &longest);
+  if (rc) return rc;
+  HIP_TRY(s->rounds.ensure(total * 8 + 8));
+  HIP_TRY(s->defer.ensure(total + 8));
+  const dh::json_cols c{s->rounds.as<uint64_t>(), s->defer.as<uint8_t>(), nullptr, nullptr, nullptr, nullptr, 4, 4, total};
+  if ((rc = store_gather_json(s, lo, nw, total, last_round, last_round, c, nullptr, 0))) return rc;
+  uint8_t d = 0;
+  if (total) HIP_TRY(hipMemcpy(&d, s->defer.p, 1, hipMemcpyDeviceToHost));
+  if (d)
+    return fail(DH_EINVAL, "the last record (key %llu) is not canonical hexjson: Last() needs the host decoder",
+                (unsigned long long)last_round);
+  return DH_OK;
+}
 
 extern "C" {
 
@@ -3367,8 +3371,7 @@ int dh_store_open_bolt_format(const uint8_t* file, size_t len, int format, dh_st
     delete s;
     return rc;
   }
-  std::lock_guard<std::mutex> lk(g_stores_mu);
-  g_stores.push_back(s);
+  handle_register(s);
   *out = s;
   return DH_OK;
 }
@@ -3386,18 +3389,7 @@ int dh_store_format_stat(const dh_store* s, uint64_t out[4]) {
   return DH_OK;
 }
 
-void dh_store_close(dh_store* s) {
-  if (!s) return;
-  {
-    std::lock_guard<std::mutex> lk(g_stores_mu);
-    g_stores.erase(std::remove(g_stores.begin(), g_stores.end(), s), g_stores.end());
-  }
-  {
-    std::lock_guard<std::mutex> lk(s->mu);
-    if (!s->dead && hipSetDevice(g_ctx.device) == hipSuccess) s->release();
-  }
-  delete s;
-}
+void dh_store_close(dh_store* s) { handle_close(s); }
 
 int dh_store_columns_device(dh_store* s, uint64_t first, uint64_t last, size_t row_stride, uint64_t* d_rounds, uint8_t* d_rows,
                             uint32_t* d_lens, size_t cap_rows, size_t* n_rows_out, uint64_t* d_missing, size_t cap_missing,
@@ -3405,7 +3397,7 @@ int dh_store_columns_device(dh_store* s, uint64_t first, uint64_t last, size_t r
   if (!s || !n_rows_out) return fail(DH_EINVAL, "null argument");
   if (!row_stride || (row_stride & 3) || row_stride > ((size_t)1 << 20))
     return fail(DH_EINVAL, "row stride %zu: a positive multiple of 4, at most 1 MiB", row_stride);
-  store_guard g(s);
+  handle_guard g(s);
   int rc = store_enter(s);
   if (rc) return rc;
   prof_wall p("store_gather_link");
@@ -3432,117 +3424,37 @@ int dh_store_check_past(dh_store* s, int scheme, const uint8_t* pk, size_t pk_le
   if (!window) return fail(DH_EINVAL, "window must be >= 1");
   const uint32_t sig_len = (uint32_t)dh_sig_len(scheme);
   const bool chained = scheme == DH_SCHEME_CHAINED;
-  store_guard g(s);
+  handle_guard g(s);
   int rc = store_enter(s);
   if (rc) return rc;
   *n_faulty_out = 0;
-  if (s->format == DH_STORE_UNTRIMMED)
-    return store_check_past_json(s, scheme, pk, pk_len, up_to, window, seed, faulty_out, cap, n_faulty_out, cb, cb_arg);
-  size_t lo, nw, total;
-  uint32_t longest;
-  // store.Last(): the largest round; the chained Get also needs the record before it (trimmed.go:156-193)
+  const bool json = s->format == DH_STORE_UNTRIMMED;
   if (!s->stat[1]) return fail(DH_ENOBEACON, "no beacon stored");
   const uint64_t last_round = s->stat[3];
-  if (chained && last_round > 0) {
-    if ((rc = store_window(s, last_round - 1, last_round, &lo, &nw, &total, &longest))) return rc;
-    if (total != 2) return fail(DH_ENOBEACON, "no beacon stored: round %llu, before the last", (unsigned long long)(last_round - 1));
-  }
-  if (last_round < up_to) up_to = last_round;
-  const uint64_t store_len = s->stat[0];
-  if (store_len <= 1) return DH_OK;
-  const uint64_t hi = std::min<uint64_t>(store_len - 1, std::max<uint64_t>(up_to, 1));  // the loop's i < len and i >= up_to
-  size_t nf = 0;
-  auto emit = [&](uint64_t r) {
-    if (nf < cap) faulty_out[nf] = r;
-    nf++;
+  if ((rc = json ? store_last_json(s, last_round) : store_last_trimmed(s, chained, last_round))) return rc;
+  // What the formats do differently inside a window. Trimmed (trimmed.go:183): the previous signature of row i is row
+  // i - 1 of the same buffer, nothing is copied twice, so a chained window is gathered from the carrier round a - 1,
+  // which is not examined. Untrimmed (BoltStore's read path, chain/boltdb/store.go:172-210): PreviousSig is the record's
+  // own field, so a missing round makes only itself faulty; a record that is not canonical is deferred (DH_DEFERRED).
+  const bool carrier = chained && !json;
+  const dbuf& prev_rows = json ? s->prevs : s->rows;
+  const dbuf& prev_lens = json ? s->prev_lens : s->lens;
+  auto gather = [&](size_t lo, size_t nw, size_t total, uint64_t g0, uint64_t b, size_t stride, size_t nmiss) {
+    if (!json)
+      return store_gather(s, lo, nw, total, g0, b, stride, s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(), total,
+                          s->missing.as<uint64_t>(), nmiss);
+    const dh::json_cols c{s->rounds.as<uint64_t>(), s->defer.as<uint8_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
+                          chained ? s->prevs.as<uint8_t>() : nullptr, chained ? s->prev_lens.as<uint32_t>() : nullptr,
+                          (uint32_t)stride, (uint32_t)stride, total};
+    return store_gather_json(s, lo, nw, total, g0, b, c, s->missing.as<uint64_t>(), nmiss);
   };
-  for (uint64_t a = 1; a <= hi;) {
-    const uint64_t b = hi - a < window - 1 ? hi : a + (window - 1);
-    if (cb) cb(a, up_to, cb_arg);
-    const uint64_t g0 = chained ? a - 1 : a;
-    size_t nmiss;
-    size_t stride;
-    {
-      prof_wall p("store_gather_link");
-      if ((rc = store_window(s, g0, b, &lo, &nw, &total, &longest))) return rc;
-      stride = ((size_t)std::max(sig_len, longest) + 3) & ~(size_t)3;
-      if (stride > 65536)
-        return fail(DH_EINVAL, "row stride %zu above 64 KiB (a %u-byte record in rounds %llu..%llu): keep the host reader", stride,
-                    longest, (unsigned long long)g0, (unsigned long long)b);
-      nmiss = window_missing(g0, b, total);
-      HIP_TRY(s->rounds.ensure(total * 8 + 8));
-      HIP_TRY(s->rows.ensure(total * stride + 8));
-      HIP_TRY(s->lens.ensure(total * 4 + 4));
-      HIP_TRY(s->missing.ensure(nmiss * 8 + 8));
-      if ((rc = store_gather(s, lo, nw, total, g0, b, stride, s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
-                             total, s->missing.as<uint64_t>(), nmiss)))
-        return rc;
-    }
-    const size_t off = chained && total ? 1 : 0, nver = total - off;
-    if (nver) {
-      prof_wall p("store_verify");
-      HIP_TRY(s->verdict.ensure(nver));
-      // previous signature of row i = row i - 1 of the same buffer (trimmed.go:183): nothing is copied twice
-      rc = dh_verify_batch_device(scheme, pk, pk_len, s->rounds.as<uint64_t>() + off, s->rows.as<uint8_t>() + off * stride, stride,
-                                  chained ? s->rows.as<uint8_t>() : nullptr, stride, chained ? s->lens.as<uint32_t>() : nullptr, nver,
-                                  s->verdict.as<uint8_t>(), nullptr, seed, nullptr, nullptr);
-      if (rc) return rc;
-    }
-    s->h_bad.resize(total);
-    s->h_rounds.resize(total);
-    s->h_missing.resize(nmiss);
-    if (total) {
-      HIP_TRY(s->bad.ensure(total));
-      HIP_TRY(dh::launch_bolt_fold(s->rounds.as<uint64_t>(), s->lens.as<uint32_t>(), s->miss_prev.as<uint8_t>(), s->verdict.as<uint8_t>(),
-                                   total, sig_len, chained ? 1 : 0, a, s->bad.as<uint8_t>(), s->st));
-      HIP_TRY(hipMemcpyAsync(s->h_bad.data(), s->bad.p, total, hipMemcpyDeviceToHost, s->st));
-      HIP_TRY(hipMemcpyAsync(s->h_rounds.data(), s->rounds.p, total * 8, hipMemcpyDeviceToHost, s->st));
-    }
-    if (nmiss) HIP_TRY(hipMemcpyAsync(s->h_missing.data(), s->missing.p, nmiss * 8, hipMemcpyDeviceToHost, s->st));
-    HIP_TRY(hipStreamSynchronize(s->st));
-    // ascending merge of the missing rounds (the carrier round a - 1 is not examined) and the rows marked bad
-    size_t im = 0;
-    while (im < nmiss && s->h_missing[im] < a) im++;
-    for (size_t i = 0; i < total; i++) {
-      if (!s->h_bad[i]) continue;
-      while (im < nmiss && s->h_missing[im] < s->h_rounds[i]) emit(s->h_missing[im++]);
-      emit(s->h_rounds[i]);
-    }
-    while (im < nmiss) emit(s->h_missing[im++]);
-    if (b == hi) break;
-    a = b + 1;
-  }
-  *n_faulty_out = nf;
-  if (nf > cap) return fail(DH_EINVAL, "%zu faulty rounds, room for %zu", nf, cap);
-  return DH_OK;
-}
-
-}  // extern "C"
-
-// BoltStore's read path (chain/boltdb/store.go:172-210) under the same loop: PreviousSig is the record's own field, so a
-// missing round makes only itself faulty; Last() fails on an empty bucket only. Entered with the handle held.
-static int store_check_past_json(dh_store* s, int scheme, const uint8_t* pk, size_t pk_len, uint64_t up_to, size_t window,
-                                 uint64_t seed, uint64_t* faulty_out, size_t cap, size_t* n_faulty_out,
-                                 void (*cb)(uint64_t round, uint64_t up_to, void* arg), void* cb_arg) {
-  const uint32_t sig_len = (uint32_t)dh_sig_len(scheme);
-  const bool chained = scheme == DH_SCHEME_CHAINED;
-  int rc;
-  size_t lo, nw, total;
-  uint32_t longest;
-  if (!s->stat[1]) return fail(DH_ENOBEACON, "no beacon stored");
-  const uint64_t last_round = s->stat[3];
-  if (s->jstat[0]) {  // Last().Round is the last record's Round field: known here only when the record is canonical
-    if ((rc = store_window(s, last_round, last_round, &lo, &nw, &total, &longest))) return rc;
-    HIP_TRY(s->rounds.ensure(total * 8 + 8));
-    HIP_TRY(s->defer.ensure(total + 8));
-    const dh::json_cols c{s->rounds.as<uint64_t>(), s->defer.as<uint8_t>(), nullptr, nullptr, nullptr, nullptr, 4, 4, total};
-    if ((rc = store_gather_json(s, lo, nw, total, last_round, last_round, c, nullptr, 0))) return rc;
-    uint8_t d = 0;
-    if (total) HIP_TRY(hipMemcpy(&d, s->defer.p, 1, hipMemcpyDeviceToHost));
-    if (d)
-      return fail(DH_EINVAL, "the last record (key %llu) is not canonical hexjson: Last() needs the host decoder",
-                  (unsigned long long)last_round);
-  }
+  auto fold = [&](size_t total, uint64_t a) {
+    if (!json)
+      return dh::launch_bolt_fold(s->rounds.as<uint64_t>(), s->lens.as<uint32_t>(), s->miss_prev.as<uint8_t>(), s->verdict.as<uint8_t>(),
+                                  total, sig_len, chained ? 1 : 0, a, s->bad.as<uint8_t>(), s->st);
+    return dh::launch_bolt_fold_json(s->lens.as<uint32_t>(), s->defer.as<uint8_t>(), s->verdict.as<uint8_t>(), total, sig_len,
+                                     s->bad.as<uint8_t>(), s->st);
+  };
   if (last_round < up_to) up_to = last_round;
   const uint64_t store_len = s->stat[0];
   if (store_len <= 1) return DH_OK;
@@ -3555,56 +3467,57 @@ static int store_check_past_json(dh_store* s, int scheme, const uint8_t* pk, siz
   for (uint64_t a = 1; a <= hi;) {
     const uint64_t b = hi - a < window - 1 ? hi : a + (window - 1);
     if (cb) cb(a, up_to, cb_arg);
-    size_t nmiss, stride;
+    const uint64_t g0 = carrier ? a - 1 : a;
+    size_t lo, nw, total, nmiss, stride;
     {
       prof_wall p("store_gather_link");
-      if ((rc = store_window(s, a, b, &lo, &nw, &total, &longest))) return rc;
-      const uint32_t longest_dec = window_longest_json(s, lo, nw);
-      stride = ((size_t)std::max(sig_len, longest_dec) + 3) & ~(size_t)3;
+      uint32_t longest;
+      if ((rc = store_window(s, g0, b, &lo, &nw, &total, &longest))) return rc;
+      if (json) longest = window_longest_json(s, lo, nw);  // rows hold the decoded fields
+      stride = ((size_t)std::max(sig_len, longest) + 3) & ~(size_t)3;
       if (stride > 65536)
-        return fail(DH_EINVAL, "row stride %zu above 64 KiB (a %u-byte field in rounds %llu..%llu): keep the host reader", stride,
-                    longest_dec, (unsigned long long)a, (unsigned long long)b);
-      nmiss = window_missing(a, b, total);
+        return fail(DH_EINVAL, "row stride %zu above 64 KiB (a %u-byte %s in rounds %llu..%llu): keep the host reader", stride, longest,
+                    json ? "field" : "record", (unsigned long long)g0, (unsigned long long)b);
+      nmiss = window_missing(g0, b, total);
       HIP_TRY(s->rounds.ensure(total * 8 + 8));
       HIP_TRY(s->rows.ensure(total * stride + 8));
       HIP_TRY(s->lens.ensure(total * 4 + 4));
-      HIP_TRY(s->defer.ensure(total + 8));
-      if (chained) {
+      if (json) HIP_TRY(s->defer.ensure(total + 8));
+      if (json && chained) {
         HIP_TRY(s->prevs.ensure(total * stride + 8));
         HIP_TRY(s->prev_lens.ensure(total * 4 + 4));
       }
       HIP_TRY(s->missing.ensure(nmiss * 8 + 8));
-      const dh::json_cols c{s->rounds.as<uint64_t>(), s->defer.as<uint8_t>(), s->rows.as<uint8_t>(), s->lens.as<uint32_t>(),
-                            chained ? s->prevs.as<uint8_t>() : nullptr, chained ? s->prev_lens.as<uint32_t>() : nullptr,
-                            (uint32_t)stride, (uint32_t)stride, total};
-      if ((rc = store_gather_json(s, lo, nw, total, a, b, c, s->missing.as<uint64_t>(), nmiss))) return rc;
+      if ((rc = gather(lo, nw, total, g0, b, stride, nmiss))) return rc;
     }
-    if (total) {
+    const size_t off = carrier && total ? 1 : 0, nver = total - off;
+    if (nver) {
       prof_wall p("store_verify");
-      HIP_TRY(s->verdict.ensure(total));
+      HIP_TRY(s->verdict.ensure(nver));
       // a deferred row is verified as the all-zero record it was left as, and its verdict is not read
-      rc = dh_verify_batch_device(scheme, pk, pk_len, s->rounds.as<uint64_t>(), s->rows.as<uint8_t>(), stride,
-                                  chained ? s->prevs.as<uint8_t>() : nullptr, stride, chained ? s->prev_lens.as<uint32_t>() : nullptr,
-                                  total, s->verdict.as<uint8_t>(), nullptr, seed, nullptr, nullptr);
+      rc = dh_verify_batch_device(scheme, pk, pk_len, s->rounds.as<uint64_t>() + off, s->rows.as<uint8_t>() + off * stride, stride,
+                                  chained ? prev_rows.as<uint8_t>() : nullptr, stride, chained ? prev_lens.as<uint32_t>() : nullptr, nver,
+                                  s->verdict.as<uint8_t>(), nullptr, seed, nullptr, nullptr);
       if (rc) return rc;
     }
     s->h_bad.resize(total);
-    s->h_defer.resize(total);
+    s->h_defer.resize(json ? total : 0);
     s->h_rounds.resize(total);
     s->h_missing.resize(nmiss);
     if (total) {
       HIP_TRY(s->bad.ensure(total));
-      HIP_TRY(dh::launch_bolt_fold_json(s->lens.as<uint32_t>(), s->defer.as<uint8_t>(), s->verdict.as<uint8_t>(), total, sig_len,
-                                        s->bad.as<uint8_t>(), s->st));
+      HIP_TRY(fold(total, a));
       HIP_TRY(hipMemcpyAsync(s->h_bad.data(), s->bad.p, total, hipMemcpyDeviceToHost, s->st));
-      HIP_TRY(hipMemcpyAsync(s->h_defer.data(), s->defer.p, total, hipMemcpyDeviceToHost, s->st));
+      if (json) HIP_TRY(hipMemcpyAsync(s->h_defer.data(), s->defer.p, total, hipMemcpyDeviceToHost, s->st));
       HIP_TRY(hipMemcpyAsync(s->h_rounds.data(), s->rounds.p, total * 8, hipMemcpyDeviceToHost, s->st));
     }
     if (nmiss) HIP_TRY(hipMemcpyAsync(s->h_missing.data(), s->missing.p, nmiss * 8, hipMemcpyDeviceToHost, s->st));
     HIP_TRY(hipStreamSynchronize(s->st));
+    for (uint8_t d : s->h_defer) ndef += d;
+    // ascending merge of the missing rounds (the carrier round a - 1 is not examined) and the rows marked bad
     size_t im = 0;
+    while (carrier && im < nmiss && s->h_missing[im] < a) im++;
     for (size_t i = 0; i < total; i++) {
-      ndef += s->h_defer[i];
       if (!s->h_bad[i]) continue;
       while (im < nmiss && s->h_missing[im] < s->h_rounds[i]) emit(s->h_missing[im++]);
       emit(s->h_rounds[i]);
@@ -3618,8 +3531,6 @@ static int store_check_past_json(dh_store* s, int scheme, const uint8_t* pk, siz
   return ndef ? DH_DEFERRED : DH_OK;
 }
 
-extern "C" {
-
 int dh_store_beacons_device(dh_store* s, uint64_t first, uint64_t last, size_t sig_stride, size_t prev_stride, uint64_t* d_rounds,
                             uint8_t* d_sigs, uint32_t* d_sig_lens, uint8_t* d_prevs, uint32_t* d_prev_lens, uint8_t* d_deferred,
                             size_t cap_rows, size_t* n_rows_out, uint64_t* d_missing, size_t cap_missing, size_t* n_missing_out,
@@ -3630,7 +3541,7 @@ int dh_store_beacons_device(dh_store* s, uint64_t first, uint64_t last, size_t s
       (want_prev && (!prev_stride || (prev_stride & 3) || prev_stride > ((size_t)1 << 20))))
     return fail(DH_EINVAL, "row strides %zu / %zu: positive multiples of 4, at most 1 MiB", sig_stride, prev_stride);
   if (!d_prevs != !d_prev_lens) return fail(DH_EINVAL, "d_prevs and d_prev_lens are given together or not at all");
-  store_guard g(s);
+  handle_guard g(s);
   int rc = store_enter(s);
   if (rc) return rc;
   if (s->format != DH_STORE_UNTRIMMED) return fail(DH_EINVAL, "not an untrimmed (hexjson) store: dh_store_columns_device serves it");
@@ -3659,7 +3570,7 @@ int dh_store_beacons_device(dh_store* s, uint64_t first, uint64_t last, size_t s
 
 int dh_store_deferred(dh_store* s, uint64_t first, uint64_t last, uint64_t* out, size_t cap, size_t* n_out) {
   if (!s || !n_out || (cap && !out)) return fail(DH_EINVAL, "null argument");
-  store_guard g(s);
+  handle_guard g(s);
   int rc = store_enter(s);
   if (rc) return rc;
   *n_out = 0;
@@ -3694,10 +3605,8 @@ int dh_store_deferred(dh_store* s, uint64_t first, uint64_t last, uint64_t* out,
 // branch levels and pages 0-3.
 
 static size_t write_window_rows() {  // DRANDHIP_STORE_WRITE_WINDOW, read at every call; default: the scan's limit
-  const char* e = getenv("DRANDHIP_STORE_WRITE_WINDOW");
-  const long long v = e ? atoll(e) : 0;
   const size_t lim = (size_t)4096 * 4096 - 2;
-  return v >= 1 && (size_t)v < lim ? (size_t)v : lim;
+  return std::min(env_size("DRANDHIP_STORE_WRITE_WINDOW", lim, 1), lim);
 }
 
 // One window's plan against `pl`, which is not changed: the record sizes of the n new rows on the device, their scan,
@@ -3927,21 +3836,6 @@ int dh_bolt_write_trimmed_device(const uint64_t* d_rounds, const uint8_t* d_rows
   return rc;
 }
 
-// entered with w->mu held
-static int writer_enter(dh_bolt_writer* w) {
-  if (w->retire.exchange(false)) w->release();
-  if (w->dead) return fail(DH_EINVAL, "writer handle invalidated by dh_shutdown (dh_bolt_writer_close it and open again)");
-  HIP_TRY(hipSetDevice(g_ctx.device));
-  return DH_OK;
-}
-struct writer_guard {
-  dh_bolt_writer* w;
-  explicit writer_guard(dh_bolt_writer* x) : w(x) { w->mu.lock(); }
-  ~writer_guard() {
-    if (w->retire.exchange(false)) w->release();
-    w->mu.unlock();
-  }
-};
 static const char* const g_writer_stage[4] = {"bolt_write_plan", "bolt_write_pack", "bolt_write_download", "bolt_write_window"};
 
 int dh_bolt_writer_open(uint32_t page_size, dh_bolt_writer** out) {
@@ -3957,8 +3851,7 @@ int dh_bolt_writer_open(uint32_t page_size, dh_bolt_writer** out) {
     return fail(DH_EDEVICE, "hipStreamCreateWithFlags: %s", hipGetErrorString(e));
   }
   w->bw.reset(page_size);
-  std::lock_guard<std::mutex> lk(g_stores_mu);
-  g_writers.push_back(w);
+  handle_register(w);
   *out = w;
   return DH_OK;
 }
@@ -3969,7 +3862,7 @@ int dh_bolt_writer_append_device(dh_bolt_writer* w, const uint64_t* d_rounds, co
   if (!w || !len_out) return fail(DH_EINVAL, "null argument");
   *len_out = 0;
   if ((n && (!d_rounds || !d_lens || (row_stride && !d_rows))) || (cap && !out)) return fail(DH_EINVAL, "null argument");
-  writer_guard g(w);
+  handle_guard g(w);
   int rc = writer_enter(w);
   if (rc) return rc;
   if (n && hip_stream) HIP_TRY(hipStreamSynchronize((hipStream_t)hip_stream));  // the columns may still be written there
@@ -3983,25 +3876,14 @@ int dh_bolt_writer_finish(dh_bolt_writer* w, uint8_t* tail_out, size_t cap, size
   if (!w || !len_out) return fail(DH_EINVAL, "null argument");
   *len_out = 0;
   if (cap && !tail_out) return fail(DH_EINVAL, "null argument");
-  writer_guard g(w);
+  handle_guard g(w);
   int rc = writer_enter(w);
   if (rc) return rc;
   const dh::boltw::cols none{nullptr, nullptr, 0, nullptr};
   return bw_append(w->bw, w->st, none, 0, true, tail_out, cap, len_out, file_off_out, head_out, stats_out, g_writer_stage);
 }
 
-void dh_bolt_writer_close(dh_bolt_writer* w) {
-  if (!w) return;
-  {
-    std::lock_guard<std::mutex> lk(g_stores_mu);
-    g_writers.erase(std::remove(g_writers.begin(), g_writers.end(), w), g_writers.end());
-  }
-  {
-    std::lock_guard<std::mutex> lk(w->mu);
-    if (!w->dead && hipSetDevice(g_ctx.device) == hipSuccess) w->release();
-  }
-  delete w;
-}
+void dh_bolt_writer_close(dh_bolt_writer* w) { handle_close(w); }
 
 struct patch_list {
   const uint64_t* rounds;
@@ -4179,7 +4061,7 @@ static const char* const g_save_stage[4] = {"store_save_plan", "store_save_pack"
 int dh_store_split(dh_store* s, uint64_t first, uint64_t last, size_t max_rows, uint64_t* bounds_out, size_t cap, size_t* n_out) {
   if (!s || !n_out || (cap && !bounds_out)) return fail(DH_EINVAL, "null argument");
   *n_out = 0;
-  store_guard g(s);
+  handle_guard g(s);
   int rc = store_enter(s);
   if (rc) return rc;
   std::vector<uint64_t> b;
@@ -4201,9 +4083,9 @@ int dh_store_save_trimmed_append(dh_store* s, dh_bolt_writer* w, uint64_t first,
   patch_list pt{patch_rounds, patch_sigs, patch_stride, patch_lens, n_patch, 0};
   int rc = patches_check(&pt, first, last);
   if (rc) return rc;
-  store_guard g(s);
+  handle_guard g(s);
   if ((rc = store_enter(s))) return rc;
-  writer_guard gw(w);
+  handle_guard gw(w);
   if ((rc = writer_enter(w))) return rc;
   bw_state& bw = w->bw;
   if (file_off_out) *file_off_out = bw.plan.next_page * bw.P;
@@ -4246,7 +4128,7 @@ int dh_store_save_trimmed(dh_store* s, uint64_t first, uint64_t last, const uint
   patch_list pt{patch_rounds, patch_sigs, patch_stride, patch_lens, n_patch, 0};
   int rc = patches_check(&pt, first, last);
   if (rc) return rc;
-  store_guard g(s);
+  handle_guard g(s);
   if ((rc = store_enter(s))) return rc;
   write_ws& ws = s->wws;
   bw_state& bw = ws.bw;
@@ -4353,13 +4235,9 @@ int dh_store_save_trimmed(dh_store* s, uint64_t first, uint64_t last, const uint
 // (k_archive.hip); a window's columns come out in the layout dh_verify_batch_device takes. Locking and lifetime as
 // dh_store.
 
-struct dh_archive {
-  std::mutex mu;
-  std::atomic<bool> retire{false};
-  bool dead = false;
+struct dh_archive : dh_handle {
   uint64_t len = 0, nrec = 0;
   uint64_t stat[7] = {0, 0, 0, 0, 0, 0, dh::ARCHIVE_TILE};
-  hipStream_t st = nullptr;
   dbuf d_file, cnt, base, scan_tmp, line_off, line_len, chunks, d_stat;
   // dh_archive_check / dh_archive_deferred: one window's columns
   dbuf rounds, sigs, sig_lens, prevs, prev_lens, rands, rand_lens, defer, verdict, rand_out, status;
@@ -4370,44 +4248,13 @@ struct dh_archive {
   bool has_id = false;
   uint32_t id_len = 0;
   dbuf d_id, meta;
-  void release() {
+  void release_buffers() override {
     for (dbuf* b : {&d_file, &cnt, &base, &scan_tmp, &line_off, &line_len, &chunks, &d_stat, &rounds, &sigs, &sig_lens, &prevs, &prev_lens,
                     &rands, &rand_lens, &defer, &verdict, &rand_out, &status, &carry, &carry_round, &carry_len, &carry_sig, &d_id, &meta})
       b->release();
-    if (st) (void)hipStreamDestroy(st);
-    st = nullptr;
-    dead = true;
   }
 };
-static std::vector<dh_archive*> g_archives;  // under g_stores_mu
-
-static void archives_shutdown() {
-  std::lock_guard<std::mutex> lk(g_stores_mu);
-  for (dh_archive* a : g_archives) {
-    if (a->mu.try_lock()) {
-      a->release();
-      a->mu.unlock();
-    } else {
-      a->retire = true;
-    }
-  }
-}
-
-// entered with a->mu held
-static int archive_enter(dh_archive* a) {
-  if (a->retire.exchange(false)) a->release();
-  if (a->dead) return fail(DH_EINVAL, "archive handle invalidated by dh_shutdown (dh_archive_close it and open again)");
-  HIP_TRY(hipSetDevice(g_ctx.device));
-  return DH_OK;
-}
-struct archive_guard {
-  dh_archive* a;
-  explicit archive_guard(dh_archive* x) : a(x) { a->mu.lock(); }
-  ~archive_guard() {
-    if (a->retire.exchange(false)) a->release();
-    a->mu.unlock();
-  }
-};
+static int archive_enter(dh_archive* a) { return handle_enter(a, "archive", "dh_archive_close"); }
 
 constexpr size_t ARCHIVE_CALL_ROWS = (size_t)4096 * 4096 - 2;  // as one store call
 
@@ -4480,6 +4327,67 @@ static void archive_clamp(const dh_archive* a, uint64_t first, size_t* n) {
   else if (*n > a->nrec - first) *n = (size_t)(a->nrec - first);
 }
 
+// the column refusals of the two chunk encoders; d_rands: the served form's digest column (null: none to align)
+static int encode_cols_check(const uint64_t* d_rounds, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_lens, const uint8_t* d_prevs,
+                             size_t prev_stride, const uint32_t* d_prev_lens, const uint8_t* d_rands, size_t n) {
+  if (!d_prevs != !d_prev_lens) return fail(DH_EINVAL, "d_prevs and d_prev_lens are given together or not at all");
+  if (n > ARCHIVE_CALL_ROWS) return fail(DH_EINVAL, "%zu rows: at most 16M rows per call: split the call", n);
+  if (n && (!d_rounds || !d_sigs || !d_sig_lens)) return fail(DH_EINVAL, "null column");
+  if (!sig_stride || (sig_stride & 3) || sig_stride > ((size_t)1 << 20) || ((uintptr_t)d_sigs & 3) || ((uintptr_t)d_rands & 3) ||
+      (d_prevs && (!prev_stride || (prev_stride & 3) || prev_stride > ((size_t)1 << 20) || ((uintptr_t)d_prevs & 3))))
+    return fail(DH_EINVAL, "rows are 4-byte aligned with strides %zu / %zu that are positive multiples of 4, at most 1 MiB", sig_stride, prev_stride);
+  return DH_OK;
+}
+
+// The chunk encoders' driver (dh_pb_encode_device, dh_rand_encode_device) on the caller's stream: upload the metadata
+// bytes (*meta_slot = their device address, read by both launches), measure every row (size), add up the chunks' bytes,
+// scan the frame lengths and write the records (encode). want_out: false measures only.
+struct encode_form {
+  const char *wall, *size_name, *encode_name;  // dh_profile stages
+  const char *one, *many;                      // what the refusals call a record
+  bool stop_empty;                             // a call that measures 0 bytes ends before the scan
+};
+template <class Size, class Encode>
+static int encode_chunks(const encode_form& f, const std::vector<uint8_t>& meta, const uint8_t** meta_slot, size_t n, hipStream_t st, Size size,
+                         Encode encode, bool want_out, size_t cap, size_t* len_out) {
+  int rc = ensure_device();
+  if (rc) return rc;
+  if (!n) return DH_OK;
+  HIP_TRY(hipSetDevice(g_ctx.device));
+  prof_wall p(f.wall);
+  HIP_TRY(hipStreamSynchronize(st));  // the columns may be written there
+  const size_t nsum = (n + 255) / 256;
+  dbuf d_meta, frame, off, scan_tmp, sums;
+  dbuf_pool pool{{&d_meta, &frame, &off, &scan_tmp, &sums}};
+  HIP_TRY(d_meta.ensure(std::max<size_t>(meta.size(), 4)));
+  HIP_TRY(frame.ensure(n * 4));
+  HIP_TRY(off.ensure((n + 1) * 4));
+  HIP_TRY(scan_tmp.ensure((n / 4096 + 2) * 4));
+  HIP_TRY(sums.ensure(nsum * sizeof(dh::pb_size_sum)));
+  if (!meta.empty()) HIP_TRY(hipMemcpyAsync(d_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, st));
+  *meta_slot = d_meta.as<uint8_t>();
+  timed_launches tl(st);
+  HIP_TRY(tl.run(f.size_name, [&] { return size(frame.as<uint32_t>(), sums.as<dh::pb_size_sum>()); }));
+  std::vector<dh::pb_size_sum> h_sums(nsum);
+  HIP_TRY(hipMemcpyAsync(h_sums.data(), sums.p, nsum * sizeof(dh::pb_size_sum), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  uint64_t total = 0;
+  for (const dh::pb_size_sum& x : h_sums) {
+    if (x.first_bad != ~0ull)
+      return fail(DH_EINVAL, "row %llu: its %s would exceed 4096 bytes, or a length passes its row's stride", (unsigned long long)x.first_bad, f.one);
+    total += x.bytes;
+  }
+  if (total >> 32) return fail(DH_EINVAL, "%llu bytes of %s: 4 GiB or more in one call: split the call", (unsigned long long)total, f.many);
+  *len_out = (size_t)total;
+  if (!want_out) return DH_OK;
+  if (cap < total) return fail(DH_EINVAL, "%llu bytes of %s, room for %zu", (unsigned long long)total, f.many, cap);
+  if (f.stop_empty && !total) return DH_OK;
+  HIP_TRY(dh::launch_scan(frame.as<uint32_t>(), n, off.as<uint32_t>(), scan_tmp.as<uint32_t>(), st));
+  HIP_TRY(tl.run(f.encode_name, [&] { return encode(off.as<uint32_t>()); }));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DH_OK;
+}
+
 extern "C" {
 
 int dh_archive_open_ndjson(const uint8_t* buf, size_t len, dh_archive** out) {
@@ -4497,8 +4405,7 @@ int dh_archive_open_ndjson(const uint8_t* buf, size_t len, dh_archive** out) {
     delete a;
     return rc;
   }
-  std::lock_guard<std::mutex> lk(g_stores_mu);
-  g_archives.push_back(a);
+  handle_register(a);
   *out = a;
   return DH_OK;
 }
@@ -4562,8 +4469,7 @@ int dh_archive_open_pb(int kind, const uint8_t* buf, size_t len, const uint64_t*
     delete a;
     return rc;
   }
-  std::lock_guard<std::mutex> lk(g_stores_mu);
-  g_archives.push_back(a);
+  handle_register(a);
   *out = a;
   return DH_OK;
 }
@@ -4573,7 +4479,7 @@ int dh_archive_kind(const dh_archive* a) { return a ? a->kind : fail(DH_EINVAL, 
 int dh_archive_set_beacon_id(dh_archive* a, const uint8_t* id, size_t id_len) {
   if (!a) return fail(DH_EINVAL, "null argument");
   if (id_len > dh::bolt::PBWIRE_MAX_RECORD) return fail(DH_EINVAL, "beacon ID of %zu bytes: no record of 4096 bytes holds it", id_len);
-  archive_guard g(a);
+  handle_guard g(a);
   int rc = archive_enter(a);
   if (rc) return rc;
   a->has_id = id != nullptr;
@@ -4608,12 +4514,8 @@ int dh_pb_encode_device(int kind, const uint64_t* d_rounds, const uint8_t* d_sig
   if (kind != DH_PB_BEACON_PACKET)
     return fail(DH_EINVAL, "record kind %d: only BeaconPacket (%d) is encoded (PublicRandResponse needs the randomness digest)", kind,
                 DH_PB_BEACON_PACKET);
-  if (!d_prevs != !d_prev_lens) return fail(DH_EINVAL, "d_prevs and d_prev_lens are given together or not at all");
-  if (n > ARCHIVE_CALL_ROWS) return fail(DH_EINVAL, "%zu rows: at most 16M rows per call: split the call", n);
-  if (n && (!d_rounds || !d_sigs || !d_sig_lens)) return fail(DH_EINVAL, "null column");
-  if (!sig_stride || (sig_stride & 3) || sig_stride > ((size_t)1 << 20) || ((uintptr_t)d_sigs & 3) ||
-      (d_prevs && (!prev_stride || (prev_stride & 3) || prev_stride > ((size_t)1 << 20) || ((uintptr_t)d_prevs & 3))))
-    return fail(DH_EINVAL, "rows are 4-byte aligned with strides %zu / %zu that are positive multiples of 4, at most 1 MiB", sig_stride, prev_stride);
+  int rc = encode_cols_check(d_rounds, d_sigs, sig_stride, d_sig_lens, d_prevs, prev_stride, d_prev_lens, nullptr, n);
+  if (rc) return rc;
   // the metadata field, the same for every row: 22 M [12 L id]
   std::vector<uint8_t> meta;
   auto varint = [&](uint64_t v) {
@@ -4634,48 +4536,14 @@ int dh_pb_encode_device(int kind, const uint64_t* d_rounds, const uint8_t* d_sig
     varint(inner.size());
     meta.insert(meta.end(), inner.begin(), inner.end());
   }
-  int rc = ensure_device();
-  if (rc) return rc;
-  if (!n) return DH_OK;
-  HIP_TRY(hipSetDevice(g_ctx.device));
-  prof_wall p("packet_encode");
-  hipStream_t st = (hipStream_t)hip_stream;
-  HIP_TRY(hipStreamSynchronize(st));  // the columns may be written there
-  const size_t nsum = (n + 255) / 256;
-  dbuf d_meta, frame, off, scan_tmp, sums;
-  struct free_all {
-    dbuf* b[5];
-    ~free_all() {
-      for (dbuf* x : b) x->release();
-    }
-  } guard{{&d_meta, &frame, &off, &scan_tmp, &sums}};
-  HIP_TRY(d_meta.ensure(std::max<size_t>(meta.size(), 4)));
-  HIP_TRY(frame.ensure(n * 4));
-  HIP_TRY(off.ensure((n + 1) * 4));
-  HIP_TRY(scan_tmp.ensure((n / 4096 + 2) * 4));
-  HIP_TRY(sums.ensure(nsum * sizeof(dh::pb_size_sum)));
-  if (!meta.empty()) HIP_TRY(hipMemcpyAsync(d_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, st));
-  const dh::pb_encode_in e{d_rounds, d_sigs, d_sig_lens, d_prevs, d_prev_lens, d_meta.as<uint8_t>(), (uint32_t)sig_stride,
-                           (uint32_t)(d_prevs ? prev_stride : 4), (uint32_t)meta.size(), delimited ? 1u : 0u};
-  timed_launches tl(st);
-  HIP_TRY(tl.run("k_pb_size", [&] { return dh::launch_pb_size(e, n, d_rec_len_out, frame.as<uint32_t>(), sums.as<dh::pb_size_sum>(), st); }));
-  std::vector<dh::pb_size_sum> h_sums(nsum);
-  HIP_TRY(hipMemcpyAsync(h_sums.data(), sums.p, nsum * sizeof(dh::pb_size_sum), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  uint64_t total = 0;
-  for (const dh::pb_size_sum& x : h_sums) {
-    if (x.first_bad != ~0ull)
-      return fail(DH_EINVAL, "row %llu: its packet would exceed 4096 bytes, or a length passes its row's stride", (unsigned long long)x.first_bad);
-    total += x.bytes;
-  }
-  if (total >> 32) return fail(DH_EINVAL, "%llu bytes of packets: 4 GiB or more in one call: split the call", (unsigned long long)total);
-  *len_out = (size_t)total;
-  if (!d_out) return DH_OK;
-  if (cap < total) return fail(DH_EINVAL, "%llu bytes of packets, room for %zu", (unsigned long long)total, cap);
-  HIP_TRY(dh::launch_scan(frame.as<uint32_t>(), n, off.as<uint32_t>(), scan_tmp.as<uint32_t>(), st));
-  HIP_TRY(tl.run("k_pb_encode", [&] { return dh::launch_pb_encode(e, n, off.as<uint32_t>(), d_out, st); }));
-  HIP_TRY(hipStreamSynchronize(st));
-  return DH_OK;
+  dh::pb_encode_in e{d_rounds, d_sigs, d_sig_lens, d_prevs, d_prev_lens, nullptr, (uint32_t)sig_stride,
+                     (uint32_t)(d_prevs ? prev_stride : 4), (uint32_t)meta.size(), delimited ? 1u : 0u};
+  const hipStream_t st = (hipStream_t)hip_stream;
+  static const encode_form enc{"packet_encode", "k_pb_size", "k_pb_encode", "packet", "packets", false};
+  return encode_chunks(
+      enc, meta, &e.meta, n, st,
+      [&](uint32_t* frame, dh::pb_size_sum* sums) { return dh::launch_pb_size(e, n, d_rec_len_out, frame, sums, st); },
+      [&](const uint32_t* off) { return dh::launch_pb_encode(e, n, off, d_out, st); }, d_out != nullptr, cap, len_out);
 }
 
 int dh_rand_encode_device(int form, const uint64_t* d_rounds, const uint8_t* d_sigs, size_t sig_stride, const uint32_t* d_sig_lens,
@@ -4690,12 +4558,8 @@ int dh_rand_encode_device(int form, const uint64_t* d_rounds, const uint8_t* d_s
   if (json && metadata) return fail(DH_EINVAL, "a RandomData record holds no metadata");
   if (flags & ~(json ? DH_ENC_NEWLINE : DH_ENC_DELIMITED))
     return fail(DH_EINVAL, "flags %d: DH_ENC_NEWLINE goes with the JSON form only, DH_ENC_DELIMITED with the protobuf form only", flags);
-  if (!d_prevs != !d_prev_lens) return fail(DH_EINVAL, "d_prevs and d_prev_lens are given together or not at all");
-  if (n > ARCHIVE_CALL_ROWS) return fail(DH_EINVAL, "%zu rows: at most 16M rows per call: split the call", n);
-  if (n && (!d_rounds || !d_sigs || !d_sig_lens)) return fail(DH_EINVAL, "null column");
-  if (!sig_stride || (sig_stride & 3) || sig_stride > ((size_t)1 << 20) || ((uintptr_t)d_sigs & 3) || ((uintptr_t)d_rands & 3) ||
-      (d_prevs && (!prev_stride || (prev_stride & 3) || prev_stride > ((size_t)1 << 20) || ((uintptr_t)d_prevs & 3))))
-    return fail(DH_EINVAL, "rows are 4-byte aligned with strides %zu / %zu that are positive multiples of 4, at most 1 MiB", sig_stride, prev_stride);
+  int rc = encode_cols_check(d_rounds, d_sigs, sig_stride, d_sig_lens, d_prevs, prev_stride, d_prev_lens, d_rands, n);
+  if (rc) return rc;
   // the metadata field, the same for every row: 2A M and the caller's marshalled common.Metadata
   std::vector<uint8_t> meta;
   if (metadata) {
@@ -4707,50 +4571,16 @@ int dh_rand_encode_device(int form, const uint64_t* d_rounds, const uint8_t* d_s
     }
     meta.insert(meta.end(), metadata, metadata + metadata_len);
   }
-  int rc = ensure_device();
-  if (rc) return rc;
-  if (!n) return DH_OK;
-  HIP_TRY(hipSetDevice(g_ctx.device));
-  prof_wall p("serve_encode");
-  hipStream_t st = (hipStream_t)hip_stream;
-  HIP_TRY(hipStreamSynchronize(st));  // the columns may be written there
-  const size_t nsum = (n + 255) / 256;
-  dbuf d_meta, frame, off, scan_tmp, sums;
-  struct free_all {
-    dbuf* b[5];
-    ~free_all() {
-      for (dbuf* x : b) x->release();
-    }
-  } guard{{&d_meta, &frame, &off, &scan_tmp, &sums}};
-  HIP_TRY(d_meta.ensure(std::max<size_t>(meta.size(), 4)));
-  HIP_TRY(frame.ensure(n * 4));
-  HIP_TRY(off.ensure((n + 1) * 4));
-  HIP_TRY(scan_tmp.ensure((n / 4096 + 2) * 4));
-  HIP_TRY(sums.ensure(nsum * sizeof(dh::pb_size_sum)));
-  if (!meta.empty()) HIP_TRY(hipMemcpyAsync(d_meta.p, meta.data(), meta.size(), hipMemcpyHostToDevice, st));
-  const dh::serve_encode_in e{d_rounds, d_sigs, d_sig_lens, d_prevs, d_prev_lens, d_rands, d_keep, d_meta.as<uint8_t>(), (uint32_t)sig_stride,
-                              (uint32_t)(d_prevs ? prev_stride : 4), (uint32_t)meta.size(),
-                              json ? dh::SERVE_RANDOM_DATA_JSON : dh::SERVE_PUBLIC_RAND_PB, flags ? 1u : 0u};
-  timed_launches tl(st);
-  HIP_TRY(tl.run("k_serve_size", [&] { return dh::launch_serve_size(e, n, d_rec_len_out, frame.as<uint32_t>(), sums.as<dh::pb_size_sum>(), st); }));
-  std::vector<dh::pb_size_sum> h_sums(nsum);
-  HIP_TRY(hipMemcpyAsync(h_sums.data(), sums.p, nsum * sizeof(dh::pb_size_sum), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  uint64_t total = 0;
-  for (const dh::pb_size_sum& x : h_sums) {
-    if (x.first_bad != ~0ull)
-      return fail(DH_EINVAL, "row %llu: its record would exceed 4096 bytes, or a length passes its row's stride", (unsigned long long)x.first_bad);
-    total += x.bytes;
-  }
-  if (total >> 32) return fail(DH_EINVAL, "%llu bytes of records: 4 GiB or more in one call: split the call", (unsigned long long)total);
-  *len_out = (size_t)total;
-  if (!d_out) return DH_OK;
-  if (cap < total) return fail(DH_EINVAL, "%llu bytes of records, room for %zu", (unsigned long long)total, cap);
-  if (!total) return DH_OK;
-  HIP_TRY(dh::launch_scan(frame.as<uint32_t>(), n, off.as<uint32_t>(), scan_tmp.as<uint32_t>(), st));
-  HIP_TRY(tl.run("k_serve_encode", [&] { return dh::launch_serve_encode(e, n, off.as<uint32_t>(), d_out, st); }));
-  HIP_TRY(hipStreamSynchronize(st));
-  return DH_OK;
+  dh::serve_encode_in e{d_rounds, d_sigs, d_sig_lens, d_prevs, d_prev_lens, d_rands, d_keep, nullptr, (uint32_t)sig_stride,
+                        (uint32_t)(d_prevs ? prev_stride : 4), (uint32_t)meta.size(),
+                        json ? dh::SERVE_RANDOM_DATA_JSON : dh::SERVE_PUBLIC_RAND_PB, flags ? 1u : 0u};
+  const hipStream_t st = (hipStream_t)hip_stream;
+  // stop_empty: a call whose rows are all dropped (d_keep) writes nothing, so no scan and no encode pass
+  static const encode_form enc{"serve_encode", "k_serve_size", "k_serve_encode", "record", "records", true};
+  return encode_chunks(
+      enc, meta, &e.meta, n, st,
+      [&](uint32_t* frame, dh::pb_size_sum* sums) { return dh::launch_serve_size(e, n, d_rec_len_out, frame, sums, st); },
+      [&](const uint32_t* off) { return dh::launch_serve_encode(e, n, off, d_out, st); }, d_out != nullptr, cap, len_out);
 }
 
 int dh_archive_stat(const dh_archive* a, uint64_t out[7]) {
@@ -4759,22 +4589,11 @@ int dh_archive_stat(const dh_archive* a, uint64_t out[7]) {
   return DH_OK;
 }
 
-void dh_archive_close(dh_archive* a) {
-  if (!a) return;
-  {
-    std::lock_guard<std::mutex> lk(g_stores_mu);
-    g_archives.erase(std::remove(g_archives.begin(), g_archives.end(), a), g_archives.end());
-  }
-  {
-    std::lock_guard<std::mutex> lk(a->mu);
-    if (!a->dead && hipSetDevice(g_ctx.device) == hipSuccess) a->release();
-  }
-  delete a;
-}
+void dh_archive_close(dh_archive* a) { handle_close(a); }
 
 int dh_archive_lines(dh_archive* a, uint64_t first_rec, size_t n_rec, uint64_t* off_out, uint32_t* len_out) {
   if (!a) return fail(DH_EINVAL, "null argument");
-  archive_guard g(a);
+  handle_guard g(a);
   int rc = archive_enter(a);
   if (rc) return rc;
   archive_clamp(a, first_rec, &n_rec);
@@ -4787,7 +4606,7 @@ int dh_archive_lines(dh_archive* a, uint64_t first_rec, size_t n_rec, uint64_t* 
 
 int dh_archive_deferred(dh_archive* a, uint64_t first_rec, size_t n_rec, uint64_t* idx_out, size_t cap, size_t* n_out) {
   if (!a || !n_out || (cap && !idx_out)) return fail(DH_EINVAL, "null argument");
-  archive_guard g(a);
+  handle_guard g(a);
   int rc = archive_enter(a);
   if (rc) return rc;
   *n_out = 0;
@@ -4824,7 +4643,7 @@ int dh_archive_beacons_device(dh_archive* a, uint64_t first_rec, size_t n_rec, s
     return fail(DH_EINVAL, "row strides %zu / %zu: positive multiples of 4, at most 1 MiB", sig_stride, prev_stride);
   if (!d_prevs != !d_prev_lens) return fail(DH_EINVAL, "d_prevs and d_prev_lens are given together or not at all");
   if (!d_rands != !d_rand_lens) return fail(DH_EINVAL, "d_rands and d_rand_lens are given together or not at all");
-  archive_guard g(a);
+  handle_guard g(a);
   int rc = archive_enter(a);
   if (rc) return rc;
   prof_wall p("archive_gather");
@@ -4847,7 +4666,7 @@ int dh_archive_check(dh_archive* a, int scheme, const uint8_t* pk, size_t pk_len
   if (anchor_round && anchor_sig_len && !anchor_sig) return fail(DH_EINVAL, "null anchor signature");
   const uint32_t sig_len = (uint32_t)dh_sig_len(scheme);
   const bool chained = scheme == DH_SCHEME_CHAINED;
-  archive_guard g(a);
+  handle_guard g(a);
   int rc = archive_enter(a);
   if (rc) return rc;
   memset(counts_out, 0, 6 * sizeof(uint64_t));
@@ -4951,15 +4770,6 @@ int dh_archive_check(dh_archive* a, int scheme, const uint8_t* pk, size_t pk_len
 // each representative once through dh_verify_batch_device, pick the first valid representative per round
 
 namespace {
-
-struct dbuf_pool {  // a call's own buffers and stream: nothing is shared between calls
-  std::vector<dbuf*> bufs;
-  hipStream_t st = nullptr;
-  ~dbuf_pool() {
-    for (dbuf* b : bufs) b->release();
-    if (st) (void)hipStreamDestroy(st);
-  }
-};
 
 // (keys, idx)[0, n) sorted by key, stably, through (keys_alt, idx_alt); *in_alt: the result lies in the alt pair. A
 // pass whose digit is the same in every key moves nothing and is skipped. Ends with the stream idle only when n < 2.

@@ -481,3 +481,34 @@ def test_two_threads_two_handles(dh, signed, tmp_path):
     for t in ths:
         t.join()
     assert not errs, errs
+
+
+# ------------------------------------------------------------------ dh_shutdown
+
+def test_shutdown_invalidates_writer(dh, tmp_path):
+    """dh_shutdown releases an open writer's device memory (closed leaves' keys, the open leaf's carried rows): its
+    handle then only accepts close, and a new writer over the same rows gives the file."""
+    from drand_amd import _lib
+    from drand_amd.store import BoltWriter, write_trimmed_bolt
+    lib = _lib.load()
+    rounds, rows, lens = columns(wc.recs(range(1, 311), 48, "down"))
+    more = [c[300:] for c in (rounds, rows, lens)]
+    rounds, rows, lens = rounds[:300], rows[:300], lens[:300]
+    out = str(tmp_path / "out.db")
+    w = BoltWriter(out, 256)
+    res = w.append(rounds, rows, lens)  # 72-byte records in 256-byte pages: many closed leaves and one open
+    assert res["rows"] == 300 and res["leaves"] > 1
+    lib.dh_shutdown()
+    try:
+        with pytest.raises(ValueError, match="dh_shutdown"):
+            w.append(*more)
+        w.close()
+    finally:
+        assert lib.dh_init(0) == 0, _lib.last_error()
+    assert not os.path.exists(out) and not os.path.exists(out + ".tmp")
+    with BoltWriter(out, 256) as again:
+        again.append(rounds, rows, lens)
+        again.finish()
+    want = str(tmp_path / "want.db")
+    write_trimmed_bolt(want, rounds, rows, lens, page_size=256)
+    assert open(out, "rb").read() == open(want, "rb").read()
