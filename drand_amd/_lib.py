@@ -70,6 +70,8 @@ SIGNATURES = {
     "dh_g1_round_prep_late_debug": (_c.c_int, [_P, _P, _c.c_size_t, _P, _P, _P]),
     "dh_msm_level0_shape_debug": (_c.c_int, [_P, _P, _P, _P]),
     "dh_field_ops_debug": (_c.c_int, [_P, _P, _c.c_size_t, _c.c_size_t, _P, _c.c_size_t]),
+    "dh_vm_debug": (_c.c_int, [_c.c_int, _P, _c.c_size_t, _P, _c.c_size_t, _c.c_size_t, _c.c_size_t, _P, _c.c_size_t,
+                               _c.c_size_t, _P, _c.c_size_t]),
     "dh_batch_begin": (_c.c_int, [_c.c_int, _c.c_char_p, _c.c_size_t, _P, _P, _c.c_size_t, _P, _c.c_size_t, _P,
                                   _c.c_size_t, _P, _P, _c.c_uint64, _P, _c.POINTER(_P), _P]),
     "dh_batch_check": (_c.c_int, [_P, _P, _c.c_size_t, _P]),

@@ -2914,6 +2914,99 @@ int dh_field_ops_debug(const uint32_t* ops, const uint32_t* in, size_t in_words,
   return DH_OK;
 }
 
+// the caller's program of dh_vm_debug, as k_vm.hip's decoder reads it: nothing it loads may lie outside the buffers
+static int vm_debug_check_program(const uint32_t* phases, size_t nphases, const uint32_t* ops, size_t nops, size_t nslots) {
+  constexpr size_t REC = dh::VM_DEBUG_REC, MAXT = dh::VM_DEBUG_MAXT, HALF = REC / 2;
+  std::vector<uint8_t> written(nslots);
+  size_t first = 0;
+  for (size_t ph = 0; ph < nphases; ph++) {
+    const uint32_t d = phases[2 * ph], kind = d & 0xff, cnt = d >> 8;
+    if (kind > 2) return fail(DH_EINVAL, "phase %zu: kind %u", ph, kind);
+    if (cnt > 64) return fail(DH_EINVAL, "phase %zu: %u ops, at most 64", ph, cnt);
+    if (kind == 2 && cnt != 1) return fail(DH_EINVAL, "phase %zu: an INV phase of %u ops", ph, cnt);
+    if (phases[2 * ph + 1] != first) return fail(DH_EINVAL, "phase %zu: first op %u is not the running sum %zu", ph, phases[2 * ph + 1], first);
+    if (first + cnt > nops) return fail(DH_EINVAL, "phase %zu: its ops end at %zu of %zu", ph, first + cnt, nops);
+    std::fill(written.begin(), written.end(), 0);
+    for (size_t k = 0; k < cnt; k++) {
+      const uint32_t* r = ops + REC * (first + k);
+      const uint32_t dst = r[0] & 0xffffu, na = (r[0] >> 16) & 0xff, nb = r[0] >> 24;
+      if (na > MAXT || nb > MAXT) return fail(DH_EINVAL, "op %zu: %u + %u terms, at most %zu a half", first + k, na, nb, MAXT);
+      if (r[HALF] != nb << 16) return fail(DH_EINVAL, "op %zu: word 16 is not the second half's count", first + k);
+      if (kind == 2 && nb) return fail(DH_EINVAL, "op %zu: an INV op with a second half", first + k);
+      if (dst >= nslots) return fail(DH_EINVAL, "op %zu: slot index %u of %zu", first + k, dst, nslots);
+      if (written[dst]) return fail(DH_EINVAL, "phase %zu: two ops write slot %u", ph, dst);
+      written[dst] = 1;
+      for (size_t j = 0; j < MAXT; j++)
+        for (size_t h = 0; h < 2; h++) {
+          const uint32_t t = r[1 + HALF * h + j];
+          if (j >= (h ? nb : na) && t) return fail(DH_EINVAL, "op %zu: a term word past its half's count is not 0", first + k);
+          if ((t & 0xffffu) >= nslots) return fail(DH_EINVAL, "op %zu: slot index %u of %zu", first + k, t & 0xffffu, nslots);
+        }
+    }
+    for (size_t k = 0; k < cnt; k++) {
+      const uint32_t* r = ops + REC * (first + k);
+      const uint32_t na = (r[0] >> 16) & 0xff, nb = r[0] >> 24;
+      for (size_t j = 0; j < MAXT; j++)
+        if ((j < na && written[r[1 + j] & 0xffffu]) || (j < nb && written[r[1 + HALF + j] & 0xffffu]))
+          return fail(DH_EINVAL, "phase %zu: op %zu reads a slot the phase writes", ph, first + k);
+    }
+    first += cnt;
+  }
+  if (first != nops) return fail(DH_EINVAL, "%zu ops given, the phases hold %zu", nops, first);
+  return DH_OK;
+}
+
+int dh_vm_debug(int tag, const uint32_t* phases, size_t nphases, const uint32_t* ops, size_t nops, size_t nslots, size_t stop,
+                const uint32_t* in, size_t in_words, size_t n, uint32_t* out, size_t out_words) {
+  if (n == 0) return DH_OK;
+  dh::vm_debug_dims d;
+  const bool committed = dh::vm_debug_shape(tag, &d);
+  if (!committed && tag != -1) return fail(DH_EINVAL, "program tag %d: 0 to 7, or -1 for the caller's program", tag);
+  if (!in || !out) return fail(DH_EINVAL, "null argument");
+  if (n > ((size_t)1 << 16)) return fail(DH_EINVAL, "more than 65536 records");
+  if (committed) {
+    nphases = (size_t)d.nphases;
+    nslots = (size_t)d.nslots;
+    nops = 0;
+    if (in_words != (size_t)d.in_words) return fail(DH_EINVAL, "input records of %zu words: the program takes %d", in_words, d.in_words);
+  } else {
+    if ((nphases && !phases) || (nops && !ops)) return fail(DH_EINVAL, "null argument");
+    if (nphases > (size_t)d.nphases) return fail(DH_EINVAL, "%zu phases: at most %d", nphases, d.nphases);
+    if (nslots == 0 || nslots > (size_t)d.nslots) return fail(DH_EINVAL, "%zu slots: 1 to %d", nslots, d.nslots);
+    if (nops > 64 * nphases) return fail(DH_EINVAL, "%zu ops given, the phases hold at most %zu", nops, 64 * nphases);
+    if (in_words != nslots * dh::VM_DEBUG_SLOT_WORDS)
+      return fail(DH_EINVAL, "slot images of %zu words: %zu slots take %zu", in_words, nslots, nslots * dh::VM_DEBUG_SLOT_WORDS);
+    int rc = vm_debug_check_program(phases, nphases, ops, nops, nslots);
+    if (rc) return rc;
+  }
+  if (stop > nphases) return fail(DH_EINVAL, "stop %zu beyond the program's %zu phases", stop, nphases);
+  if (out_words != nslots * dh::VM_DEBUG_SLOT_WORDS)
+    return fail(DH_EINVAL, "result records of %zu words: %zu slots take %zu", out_words, nslots, nslots * dh::VM_DEBUG_SLOT_WORDS);
+  lease L;
+  if (L.rc) return L.rc;
+  worker* w = L.w;
+  int rc = set_device_and_stream(w);
+  if (rc) return rc;
+  hipStream_t st = w->stream;
+  const size_t op_bytes = (nops * dh::VM_DEBUG_REC + dh::VM_DEBUG_REC / 2) * 4;  // the records, then the 16 pad words
+  HIP_TRY(w->in_sigs.ensure(2 * nphases * 4 + 4));
+  HIP_TRY(w->in_prevs.ensure(op_bytes));  // hipMalloc's alignment (256 bytes) is the records' 16
+  HIP_TRY(w->in_rounds.ensure(n * in_words * 4));
+  HIP_TRY(w->out_rand.ensure(n * out_words * 4));
+  if (!committed) {
+    if (nphases) HIP_TRY(hipMemcpyAsync(w->in_sigs.p, phases, 2 * nphases * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(w->in_prevs.p, 0, op_bytes, st));
+    if (nops) HIP_TRY(hipMemcpyAsync(w->in_prevs.p, ops, nops * dh::VM_DEBUG_REC * 4, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipMemcpyAsync(w->in_rounds.p, in, n * in_words * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(w->out_rand.p, 0, n * out_words * 4, st));
+  HIP_TRY(dh::launch_vm_debug(tag, w->in_sigs.as<uint32_t>(), (int)nphases, w->in_prevs.as<uint32_t>(), (int)nslots, (int)stop,
+                              w->in_rounds.as<uint32_t>(), in_words, n, w->out_rand.as<uint32_t>(), st));
+  HIP_TRY(hipMemcpyAsync(out, w->out_rand.p, n * out_words * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DH_OK;
+}
+
 int dh_msm_level0_shape_debug(uint64_t* rows_per_set, uint64_t* entries, int* half_a, int* half_b) {
   if (!rows_per_set || !entries || !half_a || !half_b) return fail(DH_EINVAL, "null argument");
   *rows_per_set = g_level0.rows;

@@ -215,6 +215,19 @@ hipError_t launch_leaf_check_g1j(const uint32_t* entries, size_t m, const uint32
 hipError_t launch_multi_pairing_vm(const uint32_t* P, const uint32_t* Q, size_t n, uint32_t* pairs, uint8_t* live,
                                    uint32_t* f_tmp, uint8_t* pass, hipStream_t st);
 
+// test infrastructure (k_vm.hip, dh_vm_debug): one workgroup per record runs the pairing interpreter on a
+// committed program (tag 0..7: NP1 NP2 ML1 MUL12 FE NP2C NP1J NP2J) or on the caller's (tag < 0: phases = 2 words a
+// phase, ops = REC words an op followed by 16 pad words, 16-byte aligned, both already checked), cut to `stop` phases,
+// and writes the slot image, nslots x 16 words a record. vm_debug_shape: a committed program's phase count, slot count
+// and input words per record (true), or for any other tag the caller's limits VM_MAX_PHASES and VM_SLOTS (false).
+constexpr int VM_DEBUG_REC = 32, VM_DEBUG_MAXT = 15, VM_DEBUG_SLOT_WORDS = 16;  // pairing_vm.hpp REC, MAXT; k_vm.hip SW
+struct vm_debug_dims {
+  int nphases, nslots, in_words;
+};
+bool vm_debug_shape(int tag, vm_debug_dims* d);
+hipError_t launch_vm_debug(int tag, const uint32_t* phases, int nphases, const uint32_t* ops, int nslots, int stop,
+                           const uint32_t* in, size_t in_words, size_t n, uint32_t* out, hipStream_t st);
+
 // synthetic signer: q_tmp n x 72 words and h_tmp hash_tmp_bytes(1, n) for G2 signatures (unused for G1)
 hipError_t launch_sign(int sig_g2, const uint32_t* sk, const uint64_t* rounds, const uint8_t* prevs, size_t prev_stride,
                        const uint32_t* prev_lens, const uint8_t* msgs32, size_t n, int chained, int dst_id, uint8_t* out,

@@ -574,6 +574,28 @@ int dh_msm_level0_shape_debug(uint64_t* rows_per_set, uint64_t* entries, int* ha
 int dh_field_ops_debug(const uint32_t* ops, const uint32_t* in, size_t in_words, size_t n, uint32_t* out, size_t out_words);
 
 /*
+ * Test entry (test infrastructure, no product path calls it): the lane-parallel pairing interpreter (k_vm.hip vm_exec)
+ * on n records, one 64-lane workgroup each, stopped after `stop` phases; out receives each record's whole slot image,
+ * nslots x 16 words (14 limbs of 28 bits and two pad words a slot), so out_words must be nslots x 16.
+ * tag 0..7: a committed program, in the order NP1, NP2, ML1, MUL12, FE, NP2C, NP1J, NP2J; phases, nphases, ops, nops and
+ *   nslots are ignored (the program's own hold). A record is the program's inputs in INPUT_SLOT order: 12-word
+ *   Montgomery values (radix 2^384, below p), so in_words = 12 x inputs; for MUL12 and FE the inputs are VM-form slots
+ *   of 16 words, in_words = 16 x inputs.
+ * tag -1: the caller's program. phases: 2 nphases words (kind | count << 8, then the phase's first op); ops: nops records
+ *   of 32 words in pairing_vm.hpp's layout (the entry appends the 16 pad words and aligns the buffer); a record is the
+ *   initial slot image, in_words = nslots x 16. DH_EINVAL, with nothing launched, for: nphases above the largest
+ *   committed check program's, nslots 0 or above the check kernels' slot array, a kind above 2, a count above 64, an INV
+ *   phase whose count is not 1 or whose op has a second half, more than 15 terms in a half, a first-op word that is not
+ *   the running sum of the counts, nops that is not their total, word 16 of a record that is not nb << 16, a non-zero
+ *   term word past its half's count, any slot index >= nslots, and a phase in which two ops write one slot or an op
+ *   reads a slot the phase writes.
+ * Either mode: stop above the program's phase count, a tag outside -1..7, in_words or out_words other than stated, more
+ * than 65536 records and a null pointer with n > 0 are DH_EINVAL; n = 0 succeeds. All host pointers.
+ */
+int dh_vm_debug(int tag, const uint32_t* phases, size_t nphases, const uint32_t* ops, size_t nops, size_t nslots, size_t stop,
+                const uint32_t* in, size_t in_words, size_t n, uint32_t* out, size_t out_words);
+
+/*
  * client.RandomData JSON-lines archives on the device: the records the HTTP relays serve
  * (client/random.go:5-10, marshalled through hexjson), one per line:
  *   {"round":367,"randomness":"<64 hex>","signature":"<96|192 hex>","previous_signature":"<192 hex>"}

@@ -38,30 +38,14 @@ def test_pairing_program_valid_and_committed():
         assert max(desc) < 1 << 16, tag
 
 
-def _vm_finish_model(terms):
-    """Python restatement of k_vm.hip vm_lin + vm_finish: terms (v, c) with v < 2p held as 14 x 28-bit limbs,
-    signed 64-bit per-limb sums, one signed carry pass, q = floor(top * 2^364 / p - 2^-10) in IEEE doubles, V - q p
-    in the same radix. Returns the limbs' value, which must be in [0, 2p)."""
-    import math
-    P = 0x1a0111ea397fe69a4b1ba7b6434bacd764774b84f38512bf6730d2a0f6b0f6241eabfffeb153ffffb9feffffffffaaab
-    M = (1 << 28) - 1
-    pl = [(P >> (28 * i)) & M for i in range(14)]
-    acc = [0] * 14
-    for v, c in terms:
-        for j in range(14):
-            acc[j] += c * ((v >> (28 * j)) & M)
-    limbs, c = [0] * 14, 0
-    for j in range(14):
-        t = acc[j] + c
-        limbs[j], c = t & M, t >> 28
-    top = float(c) * 268435456.0 + float(limbs[13])
-    q = math.floor(top * float.fromhex("0x1.3b06ba5e7993dp-17") - 2.0 ** -10)
-    c2 = 0
-    for j in range(14):
-        t = limbs[j] - q * pl[j] + c2
-        limbs[j], c2 = t & M, t >> 28
-    assert c + c2 == 0, "the reduced value left 14 limbs"
-    return sum(x << (28 * j) for j, x in enumerate(limbs))
+def _vm_finish_model(terms, fused):
+    """k_vm.hip vm_lin + vm_finish on terms (v, c) with v < 2p, through the interpreter's integer model
+    (tests/vm_model.py finish: signed 64-bit per-limb sums, one signed carry pass, q = floor(top * 2^364 / p - 2^-10),
+    V - q p in the same radix, the remaining carry asserted zero). fused: the quotient rounded once, as the gfx950 build
+    computes it (v_fma_f64); otherwise a rounded product and a rounded difference. Returns the limbs' value."""
+    import vm_model as m
+    acc = [sum(c * m.limbs(v)[j] for v, c in terms) for j in range(14)]
+    return m.val(m.finish(acc, fused))
 
 
 def test_lazy_linear_combination_model():
@@ -76,5 +60,6 @@ def test_lazy_linear_combination_model():
             v = rng.choice([0, 1, P - 1, P, 2 * P - 1, rng.randrange(2 * P)])
             c = rng.choice([g.MAXC, -g.MAXC, 1, -1, rng.randint(-g.MAXC, g.MAXC)])
             terms.append((v, c))
-        r = _vm_finish_model(terms)
-        assert 0 <= r < 2 * P and r % P == sum(v * c for v, c in terms) % P
+        for fused in (True, False):
+            r = _vm_finish_model(terms, fused)
+            assert 0 <= r < 2 * P and r % P == sum(v * c for v, c in terms) % P
